@@ -1,6 +1,11 @@
 """Benchmark of the MI355X OpenPose path: frames/s end-to-end (CNN + PAF grouping) at 368x368.
 
-python bench.py [--gpus N --steps K --warmup W --batch B]
+python bench.py [--gpus N --steps K --warmup W --batch B] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step and
+the workload's description).  --dump-outputs DIR also writes what the last timed step computed
+(dump_outputs).  --full adds everything else this file measures: the per-class breakdown and the 7x7
+roofline (extra profiled steps), the network-maps / fp32 / batch-1 / C5 / C4 side lines and the CPU
+baseline.
 For N > 1 launch one process per GPU (torch.distributed.run sets RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_ADDR / MASTER_PORT; nothing here imports PyTorch): frames shard round-robin over the ranks,
 and each step's per-frame result records are gathered to rank 0 by RCCL from device memory
@@ -30,7 +35,10 @@ METRIC = "frames/sec end-to-end (CNN+PAF grouping) at 368×368, 1/2/4/8 MI355X"
 FP32_MATRIX_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: FP32 matrix (= vector) peak
 BF16_DENSE_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: BF16 dense MFMA peak
 PARAMS_SCALES = [0.5, 1, 1.5, 2]  # entity.py:72 inference_scales
+N_POSE = 18 * 3  # floats of one person's pose (18 joints x (x, y, score))
 GATHER_PERSONS = 64  # persons carried per frame record (~28 KB per frame)
+DUMP_POSE_BYTES = 12 << 20  # --dump-outputs: budget of poses.npy + scores.npy ...
+DUMP_MAP_BYTES = 40 << 20  # ... and of maps.npy (the whole dump stays under 64 MB)
 
 
 def precise_net(h, w, scale, size=368, stride=8):
@@ -184,6 +192,7 @@ class Runner(object):
         # may exceed the batched post-process caps (fetch_results re-runs those frames uncapped)
         self.sync = not gather.device or bool(args.precise)
         self.pending = []  # collect flags of the gathers in flight (oldest first)
+        self.last = None  # results of the last collected step, as they reached the host (results())
         self.ctx.upload_frames(self.pool[0].array)
 
     def step(self, collect):
@@ -205,31 +214,45 @@ class Runner(object):
             res = ctx.fetch_results(0, B)
             if collect:
                 self.persons += sum(r[2].n_persons for r in res)
+                self.last = [(base + i * self.world, r[2].status, r[2].n_peaks, r[0], r[1]) for i, r in enumerate(res)]
             if self.world > 1 and not self.gather.device:
                 self.gather.g.submit([(base + i * self.world, r[2].status, r[2].n_peaks, r[0], r[1])
                                       for i, r in enumerate(res)])
-                self.pending.append(False)
+                self.pending.append(collect)
                 if len(self.pending) == 2:
-                    self.gather.g.wait()
-                    self.pending.pop(0)
+                    self._collect_host()
         self.k += 1
 
     def _collect(self):
         got = self.gather.g.wait(raw=True)  # collective: also ships every rank's overflow frames
         if self.pending.pop(0) and got is not None:  # rank 0: every rank's records of that step
             raw, overflow = got
+            self.last = got
             persons, missing = self.Fr.count_persons(raw, GATHER_PERSONS, overflow)
             self.persons += persons
             self.over_caps += missing
             self.overflow += len(overflow)
+
+    def _collect_host(self):
+        got = self.gather.g.wait()  # TCP gather: rank 0 gets every rank's whole results of that step
+        if self.pending.pop(0) and got is not None:
+            self.last = got
 
     def drain(self):
         while self.pending:
             if not self.sync:
                 self._collect()
             else:
-                self.gather.g.wait()
-                self.pending.pop(0)
+                self._collect_host()
+
+    def results(self):
+        """The last collected step's per-frame results on this rank, [(frame id, status, n_peaks,
+        poses (P,18,3), scores (P,))] by frame id: every rank's frames on rank 0 of the device-record
+        path, this rank's own on the synchronous path."""
+        if isinstance(self.last, tuple):  # (raw records, overflow results) of the device-record path
+            raw, overflow = self.last
+            return self.Fr.merge_overflow(self.Fr.unpack_records(raw, GATHER_PERSONS), overflow)
+        return sorted(self.last or [], key=lambda r: r[0])
 
     def close(self):
         for p in self.pool:
@@ -287,6 +310,46 @@ def measure(run, ctx, transport, steps, warmup, prof_7x7):
     prof = ctx.profile_read()
     ctx.profile(False)
     return elapsed, prof
+
+
+def dump_outputs(path, run, ctx, B):
+    """--dump-outputs: what the last timed step handed its caller, as float64 / float32 .npy files
+    (the inputs are seeded, so two builds run with the same arguments compare file for file):
+      frame_ids, status, n_peaks, n_persons (F,) and poses (F, P, 18, 3), scores (F, P) -- the
+        per-frame results as they reached the host, rows past a frame's n_persons zero (P = the most
+        persons of any frame; a seeded sample of the frames if they exceed DUMP_POSE_BYTES);
+      maps (K, 57, h, w) float32 and maps_frames (K,) -- the network's own 38 PAF + 19 heatmap maps
+        of that step (the averaged full-resolution maps of --precise) for a seeded sample of K staged
+        frames of this rank within DUMP_MAP_BYTES; a frame larger than that (--precise) is dumped as
+        maps (1, N) at the seeded flat positions maps_index (N,)."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(4321)
+    res = run.results()
+    P = max([len(r[4]) for r in res] + [1])
+    keep = min(len(res), max(1, DUMP_POSE_BYTES // (P * (N_POSE + 1) * 8)))
+    res = [res[i] for i in sorted(rng.choice(len(res), keep, replace=False))] if res else []
+    poses = np.zeros((len(res), P, N_POSE // 3, 3), np.float64)
+    scores = np.zeros((len(res), P), np.float64)
+    for i, r in enumerate(res):
+        poses[i, :len(r[4])] = r[3]
+        scores[i, :len(r[4])] = r[4]
+    out = {"frame_ids": [r[0] for r in res], "status": [r[1] for r in res], "n_peaks": [r[2] for r in res],
+           "n_persons": [len(r[4]) for r in res], "poses": poses, "scores": scores}
+    mh, mw = ctx.fetch_maps(0, 1)[0].shape[2:]
+    frame_bytes = 57 * mh * mw * 4
+    if frame_bytes <= DUMP_MAP_BYTES:
+        frames = sorted(rng.choice(B, min(B, DUMP_MAP_BYTES // frame_bytes), replace=False))
+        out["maps"] = np.stack([np.concatenate([m[0] for m in ctx.fetch_maps(int(f), 1)]) for f in frames])
+        out["maps_frames"] = frames
+    else:
+        flat = np.concatenate([m[0] for m in ctx.fetch_maps(0, 1)]).reshape(-1)
+        idx = np.sort(rng.integers(0, flat.size, DUMP_MAP_BYTES // 16))
+        out["maps"] = flat[idx][None]
+        out["maps_frames"] = [0]
+        out["maps_index"] = idx
+    for name, a in out.items():
+        a = np.asarray(a)
+        np.save(os.path.join(path, name + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
 
 
 def batch1_line(L, ctx, low, FH, FW, steps=60, warmup=10):
@@ -387,11 +450,13 @@ def bench_line(args, L, Wm, Fr, transport, rank, world, local):
     elapsed, prof = measure(run, ctx, transport, args.steps, args.warmup,
                             not args.no_profile and not args.graph)
     persons = run.persons
-    # per-class breakdown from a few extra (untimed) steps with every class evented
+    if args.dump_outputs and rank == 0:  # before any further step overwrites the last timed step's maps
+        dump_outputs(args.dump_outputs, run, ctx, B)
+    # --full: per-class breakdown from a few extra (untimed) steps with every class evented
+    n_extra = 3 if args.full and not args.no_profile else 0
     ctx.profile_classes(list(ctx.PROFILE_CLASSES))
-    ctx.profile(not args.no_profile)
+    ctx.profile(n_extra > 0)
     ctx.profile_reset()
-    n_extra = 0 if args.no_profile else 3
     for _ in range(n_extra):
         run.step(False)
     run.drain()
@@ -412,7 +477,7 @@ def bench_line(args, L, Wm, Fr, transport, rank, world, local):
                 "PAF post-process), batch of %d frames per GPU per step"
                 % (FW, FH, "detect_precise" if args.precise else "__call__", arith, B))
     roofline = None
-    if n7 > 0 and ms7 > 0:
+    if args.full and n7 > 0 and ms7 > 0:  # its kernel census is a step of its own
         achieved = fl7 / (ms7 * 1e-3) / 1e12
         if args.precision == "bf16x3":
             # 3 bf16 MFMA products per f32-accurate MAC: the f32-accurate peak is 2500/3 TFLOP/s
@@ -469,7 +534,7 @@ def bench_line(args, L, Wm, Fr, transport, rank, world, local):
         "stage_ms_sum": round(sum(stage_ms.values()), 3),
         "stage_ms_note": "HIP-event sums per kernel class over %d untimed profiled steps (every kernel the "
                          "step launches is in a class; the sum falls short of ms_per_step by the gaps "
-                         "between kernels)" % n_extra,
+                         "between kernels)" % n_extra if n_extra else "not measured (--full)",
         "roofline": roofline,
     }
     # the whole step against the same peak: every conv FLOP of the step / the step's wall time
@@ -499,6 +564,7 @@ def side_line(args, frame, precise, L, Wm, Fr, transport, local):
     a = argparse.Namespace(**vars(args))
     a.frame, a.precise, a.batch, a.maps, a.graph = frame, precise, None, "synthetic", 0
     a.no_variants = a.no_cpu_baseline = True
+    a.dump_outputs = None
     a.steps = args.side_steps or args.steps
     t0 = time.perf_counter()
     o, st = bench_line(a, L, Wm, Fr, transport, 0, 1, local)
@@ -540,10 +606,16 @@ def main():
     ap.add_argument("--precise", action="store_true",
                     help="C4: multi-scale detect_precise (4 scales, cubic resizes) on the staged batch "
                          "(op_run_staged_precise: one batched forward per scale)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-class stage times and the "
+                         "7x7 roofline (extra profiled steps), the side lines (network maps, fp32, batch 1, C5 "
+                         "720p, C4 multi-scale) and the CPU baseline; the --no-* options trim it")
     args = ap.parse_args()
     FH, FW = (int(v) for v in args.frame.lower().split("x"))
     headline = (FH, FW) == (368, 368) and not args.precise
-    if not headline:
+    if not headline or not args.full:
         args.no_cpu_baseline = True
         args.no_variants = True
 

@@ -19,7 +19,7 @@ for r in range(rounds):
         libs = [x for x in parts if "=" not in x and x != "base"]
         env = dict(os.environ, OP_LIB_VARIANT=libs[0] if libs else "",
                    **dict(kv.split("=", 1) for kv in parts if "=" in kv))
-        p = subprocess.run([sys.executable, os.path.join(here, "..", "bench.py"), "--no-cpu-baseline", "--no-variants", "--steps", "10",
+        p = subprocess.run([sys.executable, os.path.join(here, "..", "bench.py"), "--full", "--no-cpu-baseline", "--no-variants", "--steps", "10",
                             "--warmup", "2"] + os.environ.get("AB_BENCH_ARGS", "").split(), env=env, capture_output=True,
                            text=True, timeout=300)
         if p.returncode:

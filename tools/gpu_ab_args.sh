@@ -8,7 +8,7 @@ for r in $(seq 1 $R); do
   i=0
   for a in "$@"; do
     i=$((i + 1))
-    timeout -k 10 300 python bench.py --no-cpu-baseline --no-variants --steps 20 --warmup 3 $a > $O/v${i}_$r.log 2>&1 || exit $?
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-variants --steps 20 --warmup 3 $a > $O/v${i}_$r.log 2>&1 || exit $?
     python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], repr(sys.argv[3]), d['value'], d['ms_per_step'], (d.get('roofline') or {}).get('frac'))" $O/v${i}_$r.log $r "$a" | tee -a $O/summary.log
   done
 done

@@ -4,8 +4,8 @@ set -o pipefail
 TAG=$1; A=$2; B=$3; N=${4:-2}
 OUT=gpurun_out/ab_$TAG; mkdir -p $OUT
 for i in $(seq 1 $N); do
-  env $A timeout -k 10 200 python bench.py --no-cpu-baseline --steps 20 > $OUT/a_$i.log 2>&1 || exit $?
-  env $B timeout -k 10 200 python bench.py --no-cpu-baseline --steps 20 > $OUT/b_$i.log 2>&1 || exit $?
+  env $A timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 20 > $OUT/a_$i.log 2>&1 || exit $?
+  env $B timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 20 > $OUT/b_$i.log 2>&1 || exit $?
 done
 python - "$OUT" <<'PY'
 import json, sys, glob

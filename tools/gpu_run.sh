@@ -35,7 +35,7 @@ for step in "$@"; do
           if [ -n "$k" ]; then timeout -k 10 900 $PYT $f -m gpu -k "$k" > $log 2>&1
           else timeout -k 10 900 $PYT $f -m gpu > $log 2>&1; fi ;;
     bench) timeout -k 10 600 python -u bench.py ${arg//,/ } > $log 2>&1 ;;
-    lines) timeout -k 10 600 python -u bench.py > $log 2>&1 ;;
+    lines) timeout -k 10 600 python -u bench.py --full > $log 2>&1 ;;
     c4prof) (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
              -d $O/c4prof -o run -- python3 $GRAFT_REPO_ROOT/bench.py --precise --frame 720x1280 --steps 3 --warmup 1 \
              --no-variants --no-profile) > $log 2>&1 ;;
