@@ -33,6 +33,7 @@ EXPORTED = (
     "op_cpm_forward", "op_cpm_peaks", "op_cpm_detect", "op_cpm_detect_batch", "op_cpm_set_batch_invariant",
     "op_train_create", "op_train_destroy", "op_train_set_weights", "op_train_get_weights", "op_train_set_hyper",
     "op_train_enable_layer", "op_train_set_grad_scale", "op_train_step",
+    "op_make_labels", "op_train_step_poses", "op_train_last_label_ms",
 )
 ARCH = {"facenet": 1, "handnet": 2}
 MAX_SCALES = 8
@@ -151,6 +152,9 @@ def lib():
         "op_train_enable_layer": ([P, I32, I32], ctypes.c_int),
         "op_train_set_grad_scale": ([P, I32, D], ctypes.c_int),
         "op_train_step": ([P, P, P, P, P, P], ctypes.c_int),
+        "op_make_labels": ([I32, I32, I32, I32, I32, P, P, P, D, D, P, P, P], ctypes.c_int),
+        "op_train_step_poses": ([P, P, P, P, P, D, D, P], ctypes.c_int),
+        "op_train_last_label_ms": ([P, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -856,3 +860,44 @@ class TrainContext(object):
         losses = np.zeros(12, np.float64)
         check(lib().op_train_step(self.h_, ptr(x), ptr(pt), ptr(ht), ptr(ig), ptr(losses)), "op_train_step")
         return losses
+
+    def step_poses(self, x, poses_per_frame, mask=None, heatmap_sigma=7, paf_width=8):
+        """``step`` with the targets generated on the device from keypoints (op_train_step_poses):
+        poses_per_frame = n arrays (people, 18, 3) of (x, y, visibility) at the network input size,
+        mask (n, h, w) nonzero = ignored, or None."""
+        x = np.ascontiguousarray(x, np.float32)
+        if x.shape != (self.n, 3, self.h, self.w):
+            raise ValueError("train step: x (n,3,h,w) expected")
+        poses, offsets = pack_poses(poses_per_frame, self.n)
+        mk = pack_mask(mask, self.n, self.h, self.w)
+        losses = np.zeros(12, np.float64)
+        check(lib().op_train_step_poses(self.h_, ptr(x), ptr(poses), ptr(offsets), ptr(mk), float(heatmap_sigma),
+                                        float(paf_width), ptr(losses)), "op_train_step_poses")
+        return losses
+
+    def last_label_ms(self):
+        """Device time of the label part (uploads + kernel) of the last ``step_poses``."""
+        ms = ctypes.c_double()
+        check(lib().op_train_last_label_ms(self.h_, ctypes.byref(ms)), "op_train_last_label_ms")
+        return ms.value
+
+
+def pack_poses(poses_per_frame, n=None):
+    """n arrays (people, 18, 3) -> (poses (sum, 18, 3) f64, pose_offsets (n + 1,) i32) of op_make_labels."""
+    frames = [np.asarray(p, np.float64).reshape(-1, N_JOINTS, 3) for p in poses_per_frame]
+    if n is not None and len(frames) != n:
+        raise ValueError("expected the poses of %d frames, got %d" % (n, len(frames)))
+    offsets = np.zeros(len(frames) + 1, np.int32)
+    offsets[1:] = np.cumsum([len(p) for p in frames])
+    poses = np.ascontiguousarray(np.concatenate(frames)) if frames else np.zeros((0, N_JOINTS, 3))
+    return (poses if len(poses) else None), offsets
+
+
+def pack_mask(mask, n, h, w):
+    """None, or the (n, h, w) u8 ignore mask (nonzero = ignored) of op_make_labels."""
+    if mask is None:
+        return None
+    mk = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+    if mk.shape != (n, h, w):
+        raise ValueError("ignore mask: %s expected, got %s" % ((n, h, w), mk.shape))
+    return mk

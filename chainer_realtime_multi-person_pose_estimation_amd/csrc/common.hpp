@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <string>
 #include <type_traits>
+#include <vector>
 
 #include "openpose_hip.h"
 
@@ -340,6 +341,25 @@ int launch_connections_full(const float* paf_full, int32_t mh, int32_t mw, const
 int launch_grouping(const PostShape& s, PostBuffers& b, hipStream_t st);
 int launch_resize_images(const float* x, int32_t c, int32_t h, int32_t w, int32_t oh, int32_t ow, float* y,
                          hipStream_t st);
+
+// ---- training labels from keypoints (labels.hip) ----
+// What the host prepares for make_labels: per (frame, joint | limb) records in person order, their
+// index, and (downscale > 1) the bilinear axis taps at rec[axis_off ..].
+struct LabelHost {
+  std::vector<double> rec;
+  std::vector<int32_t> idx;  // [n][37][2]: first double in rec, record count
+  int64_t axis_off = 0;
+  int32_t oh = 0, ow = 0;
+};
+// Validates the arguments of op_make_labels / op_train_step_poses (OP_ERR_INVALID with `who` in the
+// message) and fills *out; makes no HIP call.
+int labels_pack(const char* who, int32_t n, int32_t h, int32_t w, int32_t downscale, const double* poses,
+                const int32_t* pose_offsets, double heatmap_sigma, double paf_width, LabelHost* out);
+// d_rec / d_idx: lh.rec / lh.idx on the device; d_mask (n, h, w) u8 or null; outputs are device
+// pointers, planar (n, 38 | 19 | 1, lh.oh, lh.ow), any may be null.
+int launch_make_labels(const LabelHost& lh, const double* d_rec, const int32_t* d_idx, const uint8_t* d_mask,
+                       int32_t n, int32_t h, int32_t w, int32_t downscale, double heatmap_sigma, double paf_width,
+                       float* pafs, float* heat, uint8_t* ign, hipStream_t st);
 
 // s_waitcnt vmcnt(n) for a wave-uniform run-time n (counted waits over interleaved load streams).
 __device__ __forceinline__ void wait_vm_dyn(int n) {  // n is wave-uniform

@@ -365,6 +365,14 @@ struct op_train_ctx {
   float *d_t = nullptr;
   uint8_t* d_ign = nullptr;
   float* d_x = nullptr;
+  // op_train_step_poses: label records / index / full-resolution mask on the device (grown on
+  // demand) and the events around the label work of the last such step
+  double* d_rec = nullptr;
+  int32_t* d_idx = nullptr;
+  uint8_t* d_mask = nullptr;
+  size_t rec_cap = 0;
+  hipEvent_t ev_lab[2] = {nullptr, nullptr};
+  bool lab_timed = false;
   double alpha = 1e-4, beta1 = 0.9, beta2 = 0.999, eps = 1e-8;
   bool have_weights = false;
 };
@@ -640,6 +648,91 @@ int tr_backward(op_train_ctx* c, int lowest) {
   return OP_OK;
 }
 
+// The step's device buffers (network input, targets (pafs then heat maps), ignore mask), allocated
+// at the first step.
+struct StepSizes {
+  size_t xin, tp, th, ig;
+};
+StepSizes step_sizes(const op_train_ctx* c) {
+  const size_t n = c->n, h8 = c->h / 8, w8 = c->w / 8;
+  return StepSizes{n * 3 * c->h * c->w, n * 38 * h8 * w8, n * 19 * h8 * w8, n * h8 * w8};
+}
+int tr_step_buffers(op_train_ctx* c) {
+  const StepSizes z = step_sizes(c);
+  if (!c->d_x) {
+    OP_HIP_CHECK(hipMalloc(&c->d_x, z.xin * 4));
+    OP_HIP_CHECK(hipMalloc(&c->d_t, (z.tp + z.th) * 4));
+    OP_HIP_CHECK(hipMalloc(&c->d_ign, z.ig));
+  }
+  return OP_OK;
+}
+
+// One iteration on what the stream has put into d_x, d_t and d_ign (uploaded by op_train_step,
+// d_t / d_ign generated by op_train_step_poses): forward, loss, backward, Adam; waits for the stream.
+int tr_step_core(op_train_ctx* c, double* losses) {
+  const int n = c->n, h8 = c->h / 8, w8 = c->w / 8;
+  const size_t xin = step_sizes(c).xin, tp = step_sizes(c).tp;
+  // preprocess happens on the host side of the reference (:80-86): x is the network input
+  hipLaunchKernelGGL(tr_input, dim3(nb((int64_t)xin)), dim3(256), 0, c->stream, c->d_x, c->act[T_X0], n);
+  TRC(tr_forward(c));
+  // gradients start at zero (halos too: the input-gradient convs read them)
+  OP_HIP_CHECK(hipMemsetAsync((float*)c->arena + c->grad_off, 0, c->grad_off * 4, c->stream));
+  // (no per-step gradient clearing: every enabled layer's tr_wreduce / tr_breduce assigns its whole
+  // gW / gb once per step; a disabled layer's gradients are zeroed when it is disabled)
+  // compute_loss: 6 stages x (paf, heat), mean over n * C * h8 * w8 elements each
+  const int64_t per = (int64_t)n * 38 * h8 * w8;
+  const size_t nblocks = nb(per);
+  if (c->lpart_n < 12 * nblocks) {
+    if (c->lpart) OP_HIP_CHECK(hipFree(c->lpart));
+    OP_HIP_CHECK(hipMalloc(&c->lpart, 12 * nblocks * sizeof(double)));
+    c->lpart_n = 12 * nblocks;
+  }
+  OP_HIP_CHECK(hipMemsetAsync(c->lpart, 0, 12 * nblocks * sizeof(double), c->stream));
+  for (int s = 1; s <= 6; ++s)
+    for (int paf = 1; paf >= 0; --paf) {
+      const MapT m = stage_map(s, paf);
+      const int64_t numel = (int64_t)n * m.C * h8 * w8;
+      const int slot = 2 * (s - 1) + (paf ? 0 : 1);
+      hipLaunchKernelGGL(tr_loss, dim3(nb(numel)), dim3(256), 0, c->stream, c->act[m.buf], m.off, c->grad[m.buf],
+                         paf ? c->d_t : c->d_t + tp, c->d_ign, n, m.C, (float)(2.0 / (double)numel),
+                         c->lpart + slot * nblocks);
+    }
+  // backward down to the lowest enabled layer
+  int lowest = kNL;
+  for (int l = 0; l < kNL; ++l)
+    if (c->enabled[l]) {
+      lowest = l;
+      break;
+    }
+  TRC(tr_backward(c, lowest));
+  // Adam on the enabled layers (per-layer step counters, as Chainer's per-parameter rules)
+  for (int l = 0; l < kNL; ++l) {
+    if (!c->enabled[l]) continue;
+    const TLayer& d = c->L[l];
+    const int64_t t = ++c->t_step[l];
+    const double fix1 = 1.0 - std::pow(c->beta1, (double)t), fix2 = 1.0 - std::pow(c->beta2, (double)t);
+    const float lr = (float)(c->alpha * std::sqrt(fix2) / fix1);
+    const int64_t nw = (int64_t)d.co * d.ci * d.k * d.k;
+    hipLaunchKernelGGL(tr_adam, dim3(nb(nw)), dim3(256), 0, c->stream, c->W[l], c->gW[l], c->mW[l], c->vW[l], nw,
+                       c->scale[l], lr, (float)c->beta1, (float)c->beta2, (float)c->eps);
+    hipLaunchKernelGGL(tr_adam, dim3(nb(d.co)), dim3(256), 0, c->stream, c->b[l], c->gb[l], c->mb[l], c->vb[l],
+                       (int64_t)d.co, c->scale[l], lr, (float)c->beta1, (float)c->beta2, (float)c->eps);
+  }
+  for (const auto& cv : c->convs)
+    if (c->enabled[cv.layer]) TRC(tr_pack_layer(c, cv.layer, cv));
+  std::vector<double> part(12 * nblocks);
+  OP_HIP_CHECK(hipMemcpyAsync(part.data(), c->lpart, part.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  OP_HIP_CHECK(hipStreamSynchronize(c->stream));
+  if (losses)
+    for (int k = 0; k < 12; ++k) {
+      const MapT m = stage_map(k / 2 + 1, k % 2 == 0);
+      double s = 0.0;
+      for (size_t i = 0; i < nblocks; ++i) s += part[k * nblocks + i];
+      losses[k] = s / (double)((int64_t)n * m.C * h8 * w8);
+    }
+  return OP_OK;
+}
+
 }  // namespace
 }  // namespace op
 
@@ -725,9 +818,11 @@ int op_train_destroy(op_train_ctx* c) {
     for (float* a : arrs)
       if (a) (void)hipFree(a);
   }
-  void* bufs[] = {c->arena, c->tmp, c->part, c->zeros, c->lpart, c->d_t, c->d_ign, c->d_x};
+  void* bufs[] = {c->arena, c->tmp, c->part, c->zeros, c->lpart, c->d_t, c->d_ign, c->d_x, c->d_rec, c->d_idx, c->d_mask};
   for (void* a : bufs)
     if (a) (void)hipFree(a);
+  for (hipEvent_t e : c->ev_lab)
+    if (e) (void)hipEventDestroy(e);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return OP_OK;
@@ -818,76 +913,71 @@ int op_train_step(op_train_ctx* c, const float* x, const float* pafs_t, const fl
     set_error("op_train_step: null pointer");
     return OP_ERR_INVALID;
   }
-  const int n = c->n, h8 = c->h / 8, w8 = c->w / 8;
-  const size_t xin = (size_t)n * 3 * c->h * c->w, tp = (size_t)n * 38 * h8 * w8, th = (size_t)n * 19 * h8 * w8,
-               ig = (size_t)n * h8 * w8;
-  if (!c->d_x) {
-    OP_HIP_CHECK(hipMalloc(&c->d_x, xin * 4));
-    OP_HIP_CHECK(hipMalloc(&c->d_t, (tp + th) * 4));
-    OP_HIP_CHECK(hipMalloc(&c->d_ign, ig));
+  const StepSizes z = step_sizes(c);
+  TRC(tr_step_buffers(c));
+  OP_HIP_CHECK(hipMemcpyAsync(c->d_x, x, z.xin * 4, hipMemcpyHostToDevice, c->stream));
+  OP_HIP_CHECK(hipMemcpyAsync(c->d_t, pafs_t, z.tp * 4, hipMemcpyHostToDevice, c->stream));
+  OP_HIP_CHECK(hipMemcpyAsync(c->d_t + z.tp, heat_t, z.th * 4, hipMemcpyHostToDevice, c->stream));
+  OP_HIP_CHECK(hipMemcpyAsync(c->d_ign, ignore, z.ig, hipMemcpyHostToDevice, c->stream));
+  return tr_step_core(c, losses);
+}
+
+int op_train_step_poses(op_train_ctx* c, const float* x, const double* poses, const int32_t* pose_offsets,
+                        const uint8_t* mask, double heatmap_sigma, double paf_width, double* losses) {
+  if (!c) {
+    set_error("null op_train_ctx");
+    return OP_ERR_INVALID;
   }
-  OP_HIP_CHECK(hipMemcpyAsync(c->d_x, x, xin * 4, hipMemcpyHostToDevice, c->stream));
-  OP_HIP_CHECK(hipMemcpyAsync(c->d_t, pafs_t, tp * 4, hipMemcpyHostToDevice, c->stream));
-  OP_HIP_CHECK(hipMemcpyAsync(c->d_t + tp, heat_t, th * 4, hipMemcpyHostToDevice, c->stream));
-  OP_HIP_CHECK(hipMemcpyAsync(c->d_ign, ignore, ig, hipMemcpyHostToDevice, c->stream));
-  // preprocess happens on the host side of the reference (:80-86): x is the network input
-  hipLaunchKernelGGL(tr_input, dim3(nb((int64_t)xin)), dim3(256), 0, c->stream, c->d_x, c->act[T_X0], n);
-  TRC(tr_forward(c));
-  // gradients start at zero (halos too: the input-gradient convs read them)
-  OP_HIP_CHECK(hipMemsetAsync((float*)c->arena + c->grad_off, 0, c->grad_off * 4, c->stream));
-  // (no per-step gradient clearing: every enabled layer's tr_wreduce / tr_breduce assigns its whole
-  // gW / gb once per step; a disabled layer's gradients are zeroed when it is disabled)
-  // compute_loss: 6 stages x (paf, heat), mean over n * C * h8 * w8 elements each
-  const int64_t per = (int64_t)n * 38 * h8 * w8;
-  const size_t nblocks = nb(per);
-  if (c->lpart_n < 12 * nblocks) {
-    if (c->lpart) OP_HIP_CHECK(hipFree(c->lpart));
-    OP_HIP_CHECK(hipMalloc(&c->lpart, 12 * nblocks * sizeof(double)));
-    c->lpart_n = 12 * nblocks;
+  LabelHost lh;  // (alive until the stream has been waited for: the uploads below read it)
+  TRC(labels_pack("op_train_step_poses", c->n, c->h, c->w, 8, poses, pose_offsets, heatmap_sigma, paf_width, &lh));
+  TRC(tr_check(c));
+  if (!c->have_weights) {
+    set_error("op_train_step_poses: weights not set");
+    return OP_ERR_STATE;
   }
-  OP_HIP_CHECK(hipMemsetAsync(c->lpart, 0, 12 * nblocks * sizeof(double), c->stream));
-  for (int s = 1; s <= 6; ++s)
-    for (int paf = 1; paf >= 0; --paf) {
-      const MapT m = stage_map(s, paf);
-      const int64_t numel = (int64_t)n * m.C * h8 * w8;
-      const int slot = 2 * (s - 1) + (paf ? 0 : 1);
-      hipLaunchKernelGGL(tr_loss, dim3(nb(numel)), dim3(256), 0, c->stream, c->act[m.buf], m.off, c->grad[m.buf],
-                         paf ? c->d_t : c->d_t + tp, c->d_ign, n, m.C, (float)(2.0 / (double)numel),
-                         c->lpart + slot * nblocks);
-    }
-  // backward down to the lowest enabled layer
-  int lowest = kNL;
-  for (int l = 0; l < kNL; ++l)
-    if (c->enabled[l]) {
-      lowest = l;
-      break;
-    }
-  TRC(tr_backward(c, lowest));
-  // Adam on the enabled layers (per-layer step counters, as Chainer's per-parameter rules)
-  for (int l = 0; l < kNL; ++l) {
-    if (!c->enabled[l]) continue;
-    const TLayer& d = c->L[l];
-    const int64_t t = ++c->t_step[l];
-    const double fix1 = 1.0 - std::pow(c->beta1, (double)t), fix2 = 1.0 - std::pow(c->beta2, (double)t);
-    const float lr = (float)(c->alpha * std::sqrt(fix2) / fix1);
-    const int64_t nw = (int64_t)d.co * d.ci * d.k * d.k;
-    hipLaunchKernelGGL(tr_adam, dim3(nb(nw)), dim3(256), 0, c->stream, c->W[l], c->gW[l], c->mW[l], c->vW[l], nw,
-                       c->scale[l], lr, (float)c->beta1, (float)c->beta2, (float)c->eps);
-    hipLaunchKernelGGL(tr_adam, dim3(nb(d.co)), dim3(256), 0, c->stream, c->b[l], c->gb[l], c->mb[l], c->vb[l],
-                       (int64_t)d.co, c->scale[l], lr, (float)c->beta1, (float)c->beta2, (float)c->eps);
+  if (!x) {
+    set_error("op_train_step_poses: null pointer");
+    return OP_ERR_INVALID;
   }
-  for (const auto& cv : c->convs)
-    if (c->enabled[cv.layer]) TRC(tr_pack_layer(c, cv.layer, cv));
-  std::vector<double> part(12 * nblocks);
-  OP_HIP_CHECK(hipMemcpyAsync(part.data(), c->lpart, part.size() * 8, hipMemcpyDeviceToHost, c->stream));
-  OP_HIP_CHECK(hipStreamSynchronize(c->stream));
-  if (losses)
-    for (int k = 0; k < 12; ++k) {
-      const MapT m = stage_map(k / 2 + 1, k % 2 == 0);
-      double s = 0.0;
-      for (size_t i = 0; i < nblocks; ++i) s += part[k * nblocks + i];
-      losses[k] = s / (double)((int64_t)n * m.C * h8 * w8);
-    }
+  const StepSizes z = step_sizes(c);
+  const size_t mbytes = (size_t)c->n * c->h * c->w;
+  TRC(tr_step_buffers(c));
+  if (!c->d_idx) {
+    OP_HIP_CHECK(hipMalloc(&c->d_idx, lh.idx.size() * sizeof(int32_t)));
+    OP_HIP_CHECK(hipMalloc(&c->d_mask, mbytes));
+    OP_HIP_CHECK(hipEventCreate(&c->ev_lab[0]));
+    OP_HIP_CHECK(hipEventCreate(&c->ev_lab[1]));
+  }
+  if (lh.rec.size() > c->rec_cap) {  // (no step is in flight: every step ends with a stream wait)
+    if (c->d_rec) OP_HIP_CHECK(hipFree(c->d_rec));
+    c->d_rec = nullptr;
+    c->rec_cap = 0;
+    OP_HIP_CHECK(hipMalloc(&c->d_rec, 2 * lh.rec.size() * sizeof(double)));
+    c->rec_cap = 2 * lh.rec.size();
+  }
+  OP_HIP_CHECK(hipMemcpyAsync(c->d_x, x, z.xin * 4, hipMemcpyHostToDevice, c->stream));
+  c->lab_timed = false;
+  OP_HIP_CHECK(hipEventRecord(c->ev_lab[0], c->stream));
+  OP_HIP_CHECK(hipMemcpyAsync(c->d_rec, lh.rec.data(), lh.rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  OP_HIP_CHECK(hipMemcpyAsync(c->d_idx, lh.idx.data(), lh.idx.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  if (mask) OP_HIP_CHECK(hipMemcpyAsync(c->d_mask, mask, mbytes, hipMemcpyHostToDevice, c->stream));
+  TRC(launch_make_labels(lh, c->d_rec, c->d_idx, mask ? c->d_mask : nullptr, c->n, c->h, c->w, 8, heatmap_sigma,
+                         paf_width, c->d_t, c->d_t + z.tp, c->d_ign, c->stream));
+  OP_HIP_CHECK(hipEventRecord(c->ev_lab[1], c->stream));
+  TRC(tr_step_core(c, losses));
+  c->lab_timed = true;
+  return OP_OK;
+}
+
+int op_train_last_label_ms(op_train_ctx* c, double* ms) {
+  TRC(tr_check(c));
+  if (!ms || !c->lab_timed) {
+    set_error("op_train_last_label_ms: no completed op_train_step_poses");
+    return !ms ? OP_ERR_INVALID : OP_ERR_STATE;
+  }
+  float t = 0.0f;
+  OP_HIP_CHECK(hipEventElapsedTime(&t, c->ev_lab[0], c->ev_lab[1]));
+  *ms = (double)t;
   return OP_OK;
 }
 

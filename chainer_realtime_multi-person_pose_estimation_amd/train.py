@@ -14,6 +14,10 @@ The COCO data pipeline (coco_data_loader.py, pycocotools, getData.sh) needs the 
 network: ``synthetic_batch`` stands in with seeded images and COCO-like maps of random skeletons
 (Gaussian heat peaks + unit-vector PAFs on the limbs, the reference's label formulas restated).
 
+``--data poses`` trains from keypoints instead: ``synthetic_poses`` draws integer-valued
+(people, 18, 3) poses as parse_coco_annotation makes them, and ``Updater.update_poses`` has the
+device generate the targets from them inside the step (labels.py, op_train_step_poses).
+
     python -m chainer_realtime_multi-person_pose_estimation_amd.train --batchsize 4 --iteration 10
 """
 import argparse
@@ -27,6 +31,7 @@ import numpy as np
 from . import _lib
 from . import weights as _weights
 from .constants import params
+from .labels import train_params
 
 VGG_FROZEN = ["conv1_1", "conv1_2", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3", "conv3_4", "conv4_1",
               "conv4_2"]
@@ -100,16 +105,30 @@ class Updater(object):
     def disable_update(self, name):
         self.ctx.enable(self.names.index(name), False)
 
-    def update(self, batch):
-        """batch = (imgs (n,h,w,3) u8, pafs (n,38,h/8,w/8), heatmaps (n,19,h/8,w/8), ignore_mask (n,h/8,w/8)).
-        Returns (loss, paf_loss_log, heatmap_loss_log) as compute_loss does."""
+    def _schedule(self):
         if self.iteration == 2000:
             for name in VGG_FROZEN:
                 self.enable_update(name)
         self.alpha = alpha_at(self.iteration, self.alpha)
         self.ctx.set_hyper(self.alpha, self.beta1, self.beta2, self.eps)
+
+    def update(self, batch):
+        """batch = (imgs (n,h,w,3) u8, pafs (n,38,h/8,w/8), heatmaps (n,19,h/8,w/8), ignore_mask (n,h/8,w/8)).
+        Returns (loss, paf_loss_log, heatmap_loss_log) as compute_loss does."""
+        self._schedule()
         imgs, pafs, heatmaps, ignore_mask = batch
-        losses = self.ctx.step(preprocess(imgs), pafs, heatmaps, ignore_mask)
+        return self._log(self.ctx.step(preprocess(imgs), pafs, heatmaps, ignore_mask))
+
+    def update_poses(self, imgs, poses_per_frame, mask=None):
+        """``update`` from what the reference's loader holds before generate_labels' last three
+        lines (coco_data_loader.py:338-340): imgs (n,h,w,3) u8 at the network input size, per frame
+        the (people, 18, 3) poses at that size, and the (n,h,w) ignore mask before its dilation
+        (None: nothing ignored).  The device makes the targets and runs the iteration."""
+        self._schedule()
+        return self._log(self.ctx.step_poses(preprocess(imgs), poses_per_frame, mask,
+                                             train_params["heatmap_sigma"], train_params["paf_sigma"]))
+
+    def _log(self, losses):
         self.iteration += 1
         paf_log = [float(v) for v in losses[0::2]]
         heat_log = [float(v) for v in losses[1::2]]
@@ -160,6 +179,18 @@ def synthetic_batch(rng, n, h, w, people=3):
     return imgs, paf, heat, ignore
 
 
+def synthetic_poses(rng, n, h, w, people=4):
+    """Seeded stand-in for parse_coco_annotation + augmentation: per frame a (people, 18, 3) int32
+    array, skeletons scattered around a body centre, visibility from {0, 1, 2}."""
+    out = []
+    for _ in range(n):
+        c = rng.uniform([0.2 * w, 0.2 * h], [0.8 * w, 0.8 * h], (people, 1, 2))
+        xy = c + rng.normal(0, 0.12 * min(h, w), (people, 18, 2))
+        vis = rng.integers(0, 3, (people, 18, 1))
+        out.append(np.concatenate([xy, vis], axis=2).astype(np.int32))
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Train pose estimation (MI355X, synthetic data)")
     ap.add_argument("--arch", "-a", choices=["posenet"], default="posenet")
@@ -171,6 +202,9 @@ def main(argv=None):
     ap.add_argument("--resume", action="store_true", help="do not freeze the VGG layers")
     ap.add_argument("--out", "-o", default="result/test")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--data", choices=["maps", "poses"], default="maps",
+                    help="maps: host-made synthetic target maps; poses: synthetic keypoints, targets made on the device")
+    ap.add_argument("--people", type=int, default=4, help="people per frame (--data poses)")
     args = ap.parse_args(argv)
     model = _weights.load_npz(args.initmodel) if args.initmodel else _weights.random_weights(args.seed)
     up = Updater(args.batchsize, args.insize, args.insize, model=model, device=max(args.gpu, 0), resume=args.resume)
@@ -178,14 +212,26 @@ def main(argv=None):
     os.makedirs(args.out, exist_ok=True)
     log = []
     for it in range(args.iteration):
-        batch = synthetic_batch(rng, args.batchsize, args.insize, args.insize)
-        t0 = time.perf_counter()
-        loss, pl, hl = up.update(batch)
-        dt = time.perf_counter() - t0
-        log.append({"iteration": up.iteration, "main/loss": loss, "main/paf": sum(pl), "main/heat": sum(hl),
-                    "elapsed_s": dt})
-        print("iter %d loss %.6f paf %.6f heat %.6f (%.1f ms)" % (up.iteration, loss, sum(pl), sum(hl), dt * 1e3),
-              flush=True)
+        if args.data == "poses":
+            imgs = rng.integers(0, 256, (args.batchsize, args.insize, args.insize, 3), dtype=np.uint8)
+            poses = synthetic_poses(rng, args.batchsize, args.insize, args.insize, args.people)
+            mask = rng.random((args.batchsize, args.insize, args.insize)) < 0.0005
+            t0 = time.perf_counter()
+            loss, pl, hl = up.update_poses(imgs, poses, mask)
+            dt = time.perf_counter() - t0
+            label_ms = up.ctx.last_label_ms()  # device events around the label uploads + kernel
+            extra = {"label_ms": label_ms, "step_ms": dt * 1e3 - label_ms}
+            note = ", labels %.3f ms, step %.1f ms" % (label_ms, dt * 1e3 - label_ms)
+        else:
+            batch = synthetic_batch(rng, args.batchsize, args.insize, args.insize)
+            t0 = time.perf_counter()
+            loss, pl, hl = up.update(batch)
+            dt = time.perf_counter() - t0
+            extra, note = {}, ""
+        log.append(dict({"iteration": up.iteration, "main/loss": loss, "main/paf": sum(pl), "main/heat": sum(hl),
+                         "elapsed_s": dt}, **extra))
+        print("iter %d loss %.6f paf %.6f heat %.6f (%.1f ms%s)" % (up.iteration, loss, sum(pl), sum(hl), dt * 1e3,
+                                                                    note), flush=True)
     with open(os.path.join(args.out, "log"), "w") as f:
         json.dump(log, f, indent=1)
     _weights.save_npz(os.path.join(args.out, "model_iter_%d.npz" % up.iteration), up.weights())

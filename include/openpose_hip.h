@@ -450,6 +450,29 @@ int op_train_set_grad_scale(op_train_ctx* ctx, int32_t layer, double scale);
 int op_train_step(op_train_ctx* ctx, const float* x, const float* pafs_t, const float* heat_t, const uint8_t* ignore,
                   double* losses);
 
+/* ---- Training labels from keypoint annotations (coco_data_loader.py:208-268, :340) ----
+ * poses: sum(counts) x 18 x 3 f64 (x, y, visibility; a joint counts when visibility > 0), frame f's
+ * people at pose_offsets[f] .. pose_offsets[f+1] (pose_offsets[0] = 0, n + 1 entries); mask (n, h, w)
+ * u8, nonzero = ignored, may be null (no ignored pixels); outputs are host pointers, any may be null.
+ * Heat maps: per joint the max over people of exp(-0.5 d^2 / heatmap_sigma^2), channel 18 = 1 - the
+ * max over all joints; PAFs: the unit limb vector within paf_width of the limb, averaged over the
+ * people whose limb covers the pixel; ignore: the mask dilated by ones((16, 16)) (cv2.MORPH_DILATE).
+ * downscale 1: those maps at h x w.  downscale d > 1 (h % d == 0, w % d == 0, h/d, w/d >= 2): the
+ * (h/d, w/d) maps F.resize_images would make of them (compute_loss, train_coco_pose_estimation.py:
+ * 56-60: targets resized, mask = resize(mask) > 0), evaluated at the four bilinear taps of every
+ * output pixel only.  Arguments are validated before any device call (OP_ERR_INVALID). */
+int op_make_labels(int32_t device, int32_t n, int32_t h, int32_t w, int32_t downscale, const double* poses,
+                   const int32_t* pose_offsets, const uint8_t* mask, double heatmap_sigma, double paf_width,
+                   float* pafs /* n,38,oh,ow */, float* heatmaps /* n,19,oh,ow */, uint8_t* ignore /* n,oh,ow */);
+/* op_train_step with the targets generated on the device: the downscale-8 labels of (poses,
+ * pose_offsets, mask (n, h, w) or null) are written on the context's stream straight into the
+ * step's target and ignore buffers, then the same iteration runs. */
+int op_train_step_poses(op_train_ctx* ctx, const float* x, const double* poses, const int32_t* pose_offsets,
+                        const uint8_t* mask /* n,h,w */, double heatmap_sigma, double paf_width, double* losses);
+/* Device time (ms, stream events) of the label part of the last op_train_step_poses: the uploads of
+ * the pose records and the mask plus the label kernel.  OP_ERR_STATE before the first such step. */
+int op_train_last_label_ms(op_train_ctx* ctx, double* ms);
+
 #ifdef __cplusplus
 }
 #endif
