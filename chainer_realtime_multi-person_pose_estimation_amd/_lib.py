@@ -21,7 +21,8 @@ N_JOINTS, N_LIMBS, N_PAF, N_HEAT, N_LAYERS = 18, 19, 38, 19, 92
 # Every symbol include/openpose_hip.h declares (checked by tests/test_abi.py).
 EXPORTED = (
     "op_last_error", "op_build_info", "op_default_params", "op_default_limits", "op_layer_info", "op_create", "op_destroy",
-    "op_set_weights", "op_detect", "op_preprocess", "op_forward", "op_forward_stages", "op_resize_images", "op_compute_peaks",
+    "op_set_weights", "op_detect", "op_preprocess", "op_forward", "op_forward_stages", "op_forward_probe",
+    "op_forward_probe_info", "op_resize_images", "op_compute_peaks",
     "op_compute_connections", "op_grouping", "op_postprocess", "op_stage_frames", "op_stage_maps",
     "op_use_staged_maps", "op_run_staged", "op_run_staged_graph", "op_graph_info", "op_synchronize", "op_fetch_result",
     "op_last_timing", "op_forward_flops", "op_profile_enable", "op_profile_read", "op_profile_reset",
@@ -98,6 +99,8 @@ def lib():
         "op_preprocess": ([P, P, I32, I32, I64, I32, I32, P], ctypes.c_int),
         "op_forward": ([P, P, I32, I32, I32, P, P], ctypes.c_int),
         "op_forward_stages": ([P, P, I32, I32, I32, P, P], ctypes.c_int),
+        "op_forward_probe": ([P, P, I32, I32, I32, I32, I32, I32, P, I64], ctypes.c_int),
+        "op_forward_probe_info": ([I32, ctypes.POINTER(ctypes.c_char_p), P, P], ctypes.c_int),
         "op_resize_images": ([P, P, I32, I32, I32, I32, I32, P], ctypes.c_int),
         "op_compute_peaks": ([P, P, I32, I32, I32, P, I64, P], ctypes.c_int),
         "op_compute_connections": ([P, P, I32, I32, P, I64, D, P, I64, P], ctypes.c_int),
@@ -277,6 +280,22 @@ def layer_table():
     for i in range(N_LAYERS):
         check(lib().op_layer_info(i, ctypes.byref(name), ctypes.byref(ci), ctypes.byref(co), ctypes.byref(k)))
         out.append((name.value.decode(), ci.value, co.value, k.value))
+    return out
+
+
+N_PROBE_POINTS = 46
+
+
+def probe_table():
+    """[(name, channels, divisor)] of op_forward_probe's points 0 .. 45, from the library: the point's
+    tensor is (frames, channels, h / divisor, w / divisor)."""
+    out = []
+    name = ctypes.c_char_p()
+    ch, div = ctypes.c_int32(), ctypes.c_int32()
+    for i in range(N_PROBE_POINTS):
+        check(lib().op_forward_probe_info(i, ctypes.byref(name), ctypes.byref(ch), ctypes.byref(div)),
+              "op_forward_probe_info")
+        out.append((name.value.decode(), ch.value, div.value))
     return out
 
 
@@ -460,6 +479,21 @@ class Context(object):
         heat = np.empty((6, n, N_HEAT, h // 8, w // 8), np.float32)
         check(lib().op_forward_stages(self.h, ptr(x), n, h, w, ptr(paf), ptr(heat)), "op_forward_stages")
         return paf, heat
+
+    def forward_probe(self, x, point, frames=None):
+        """What probe point `point` of the forward wrote (include/openpose_hip.h: op_forward_probe), as
+        dense f32 (frames, channels, h / divisor, w / divisor); frames = (first, count), default all."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n, c, h, w = x.shape
+        if c != 3:
+            raise ValueError("expected (n, 3, h, w)")
+        f0, nf = (0, n) if frames is None else (int(frames[0]), int(frames[1]))
+        name, ch, div = ctypes.c_char_p(), ctypes.c_int32(), ctypes.c_int32()
+        check(lib().op_forward_probe_info(int(point), ctypes.byref(name), ctypes.byref(ch), ctypes.byref(div)),
+              "op_forward_probe_info")
+        out = np.empty((max(nf, 0), ch.value, h // div.value, w // div.value), np.float32)
+        check(lib().op_forward_probe(self.h, ptr(x), n, h, w, int(point), f0, nf, ptr(out), out.size), "op_forward_probe")
+        return out
 
     def resize_images(self, x, oh, ow):
         x = np.ascontiguousarray(x, dtype=np.float32)

@@ -189,6 +189,15 @@ int launch_preprocess_split(const uint8_t* frames, int64_t frame_bytes, int64_t 
                             int32_t sw, int32_t dh, int32_t dw, float* out, hipStream_t st, float div = 255.0f);
 int launch_extract_maps32(const float* m, int32_t cs, int32_t heat_off, int32_t n, int32_t h, int32_t w, float* paf,
                           float* heat, hipStream_t st);
+// An activation tensor as op_forward_probe's extraction reads it (runtime.hip Act): fmt 0 f32
+// [hp][wp][cs], 1 split [hp][wp][cs] (8 hi then 8 lo bf16 per 8 channels), 2 split chunk-planar
+struct ActView {
+  int32_t fmt, pad, cs, h, w;
+};
+// channels [c0, c0 + nc) (c0 a multiple of 8) of frames [f0, f0 + nf) of the n-frame tensor `in` ->
+// dense f32 dst[f - f0][dst_c0 + c - c0][y][x] with dst_ch channels per frame
+int launch_extract_act(const float* in, const ActView& a, int32_t n, int32_t f0, int32_t nf, int32_t c0, int32_t nc,
+                       float* dst, int32_t dst_c0, int32_t dst_ch, hipStream_t st);
 int launch_maxpool2(const float* in, int32_t pin, float* out, int32_t pout, int32_t n, int32_t h, int32_t w,
                     int32_t c, hipStream_t st);
 int launch_nchw_to_nhwc8(const float* x, float* out, int32_t n, int32_t h, int32_t w, hipStream_t st);

@@ -457,4 +457,66 @@ int launch_extract_maps32(const float* m, int32_t cs, int32_t heat_off, int32_t 
   return OP_OK;
 }
 
+// op_forward_probe: channels [c0, c0 + nc) of frames [f0, f0 + nf) of an activation tensor -> dense
+// f32 planar dst[f - f0][dst_c0 + c - c0][y][x] (dst_ch channels per frame).  One thread per
+// (frame, 8-channel group, pixel): fmt 0 reads 8 floats of the f32 [hp][wp][cs] layout, fmt 1 / 2 the
+// group's hi and lo pieces of the split layout ([hp][wp][cs] / chunk-planar) and returns hi + lo.
+__global__ __launch_bounds__(256) void extract_act(const char* __restrict__ in, ActView a, int f0, int nf, int c0, int nc,
+                                                   float* __restrict__ dst, int dst_c0, int dst_ch) {
+  const int groups = (nc + 7) / 8;
+  const int64_t total = (int64_t)nf * groups * a.h * a.w;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int x = (int)(i % a.w);
+  const int y = (int)((i / a.w) % a.h);
+  const int g = (int)((i / ((int64_t)a.w * a.h)) % groups);
+  const int f = (int)(i / ((int64_t)a.w * a.h * groups));
+  const int hp = a.h + 2 * a.pad, wp = a.w + 2 * a.pad;
+  const char* fb = in + (int64_t)(f0 + f) * hp * wp * a.cs * 4;
+  const int64_t pix = (int64_t)(y + a.pad) * wp + (x + a.pad);
+  const int c = c0 + 8 * g;
+  float v[8];
+  if (a.fmt == 0) {
+    const float* p = (const float*)fb + pix * a.cs + c;
+    const floatx4 v0 = *(const floatx4*)p, v1 = *(const floatx4*)(p + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[e] = v0[e];
+      v[e + 4] = v1[e];
+    }
+  } else {
+    const int piece = (c >> 3) * 2;  // the group's hi piece; its lo piece is the next one
+    const int64_t ps = split_piece_stride(a.fmt == 2, hp, wp);
+    const char* p = fb + piece * ps + pix * split_pixel_stride(a.fmt == 2, a.cs);
+    const u16x4 h0 = *(const u16x4*)p, h1 = *(const u16x4*)(p + 8);
+    const u16x4 l0 = *(const u16x4*)(p + ps), l1 = *(const u16x4*)(p + ps + 8);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[e] = bf16_to_f(h0[e]) + bf16_to_f(l0[e]);
+      v[e + 4] = bf16_to_f(h1[e]) + bf16_to_f(l1[e]);
+    }
+  }
+  float* o = dst + (((int64_t)f * dst_ch + dst_c0 + 8 * g) * a.h + y) * a.w + x;
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+    if (8 * g + e < nc) o[(int64_t)e * a.h * a.w] = v[e];
+}
+
+int launch_extract_act(const float* in, const ActView& a, int32_t n, int32_t f0, int32_t nf, int32_t c0, int32_t nc,
+                       float* dst, int32_t dst_c0, int32_t dst_ch, hipStream_t st) {
+  // every 8-channel group read lies inside the pixel's cs channels, every frame inside the tensor
+  if (a.fmt < 0 || a.fmt > 2 || a.h < 1 || a.w < 1 || a.pad < 0 || a.cs % 8 || c0 % 8 || c0 < 0 || nc < 1 ||
+      c0 + (nc + 7) / 8 * 8 > a.cs || (a.fmt == 2 && a.cs % 16) || f0 < 0 || nf < 1 || f0 + nf > n || dst_c0 < 0 ||
+      dst_c0 + nc > dst_ch) {
+    set_error("extract_act: bad channel or frame range");
+    return OP_ERR_INVALID;
+  }
+  const int64_t total = (int64_t)nf * ((nc + 7) / 8) * a.h * a.w;
+  hipLaunchKernelGGL(extract_act, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const char*)in, a, f0, nf, c0,
+                     nc, dst, dst_c0, dst_ch);
+  OP_AFTER_LAUNCH("extract_act", st);
+  OP_HIP_CHECK(hipGetLastError());
+  return OP_OK;
+}
+
 }  // namespace op

@@ -881,13 +881,82 @@ static int pool(op_ctx* c, const Act& in, const Act& out, int ch) {
   });
 }
 
+// Whether this forward runs stages 2-6 on the chunk-planar buffers (see run_forward).
+static bool stages_planar(const op_ctx* c) {
+  const int sh8 = c->buf[B_BRA].h, sw8 = c->buf[B_BRA].w;
+  return c->split && (c->conv_algo == 4 || c->conv_algo == 5) && c->stage_planar && head_fused_on() &&
+         conv_m16_takes(c->gn, sh8, sw8, 1, 256) && conv_m16_takes(c->gn, sh8, sw8, 2, 128);
+}
+
+// ---- probe points (op_forward_probe): the launch boundaries of run_forward in execution order ----
+// (name, channels returned, size divisor); map points return paf 38 | heat 19 | feature 128, the
+// reference's F.concat order (CocoPoseNet.py:168)
+struct ProbeInfo {
+  const char* name;
+  int channels, div;
+};
+constexpr int kProbePoints = 46;
+static ProbeInfo probe_info(int point) {
+  static const ProbeInfo head[16] = {
+      {"input", 3, 1},          {"conv1_2+pool", 64, 2},  {"conv2_1", 128, 2},      {"conv2_2+pool", 128, 4},
+      {"conv3_1", 256, 4},      {"conv3_2", 256, 4},      {"conv3_3", 256, 4},      {"conv3_4+pool", 256, 8},
+      {"conv4_1", 512, 8},      {"conv4_2", 512, 8},      {"conv4_3_CPM", 256, 8},  {"conv4_4_CPM", 128, 8},
+      {"conv5_1", 256, 8},      {"conv5_2", 256, 8},      {"conv5_3", 256, 8},      {"stage1", 185, 8}};
+  if (point < 16) return head[point];
+  static const char* const names[5][6] = {
+      {"Mconv1_stage2", "Mconv2_stage2", "Mconv3_stage2", "Mconv4_stage2", "Mconv5_stage2", "stage2"},
+      {"Mconv1_stage3", "Mconv2_stage3", "Mconv3_stage3", "Mconv4_stage3", "Mconv5_stage3", "stage3"},
+      {"Mconv1_stage4", "Mconv2_stage4", "Mconv3_stage4", "Mconv4_stage4", "Mconv5_stage4", "stage4"},
+      {"Mconv1_stage5", "Mconv2_stage5", "Mconv3_stage5", "Mconv4_stage5", "Mconv5_stage5", "stage5"},
+      {"Mconv1_stage6", "Mconv2_stage6", "Mconv3_stage6", "Mconv4_stage6", "Mconv5_stage6", "stage6"}};
+  const int st = (point - 16) / 6, i = (point - 16) % 6;
+  return ProbeInfo{names[st][i], i == 5 ? 185 : 256, 8};
+}
+
+// Extract what probe point `point` wrote (frames [f0, f0 + nf)) as dense f32 NCHW into d_out.
+static int probe_extract(op_ctx* c, int point, int f0, int nf, float* d_out) {
+  const Act* B = c->buf;
+  const bool planar = stages_planar(c);
+  auto view = [&](const Act& a) { return ActView{c->split ? (a.planar ? 2 : 1) : 0, a.pad, a.cs, a.h, a.w}; };
+  auto take = [&](const Act& a, int c0, int nc, int dst_c0, int dst_ch) {
+    return launch_extract_act(a.p, view(a), c->gn, f0, nf, c0, nc, d_out, dst_c0, dst_ch, c->stream);
+  };
+  const int i = point < 16 ? -1 : (point - 16) % 6;
+  if (point == 15 || i == 5) {  // the buffer the next stage's Mconv1 reads
+    const Act& m = planar ? B[B_CATP] : B[B_CAT];
+    RC(take(m, kCatPaf, 38, 0, 185));
+    RC(take(m, kCatHeat, 19, 38, 185));
+    return take(m, kCatFeat, 128, 57, 185);
+  }
+  if (point >= 16) {  // Mconv1, 3, 5 write SA, Mconv2, 4 SB
+    const Act& a = (i % 2 == 0) ? (planar ? B[B_PA] : B[B_BRA]) : (planar ? B[B_PB] : B[B_BRB]);
+    return take(a, 0, 256, 0, 256);
+  }
+  static const int buf_of[15] = {B_X0, B_P1, B_C21, B_P2, B_C3A, B_C3B, B_C3A, B_P3, B_C41, B_C42, B_C43, B_CAT,
+                                 B_BRA, B_BRB, B_BRA};
+  const int nc = probe_info(point).channels;
+  return take(B[buf_of[point]], point == 11 ? kCatFeat : 0, nc, 0, nc);
+}
+
 // frames != nullptr (split path): conv1_1 reads the uint8 frames directly (fused input kernel).
 // stages != nullptr: every stage's (paf, heat) is also extracted to stages = paf [6][n][38][lh][lw]
 // followed by heat [6][n][19][lh][lw] (op_forward_stages; the reference's pafs / heatmaps lists).
+// stop_point >= 0 (op_forward_probe only): return right after probe point stop_point (kProbe); the
+// default never matches the point counter, so every other caller launches the whole forward.
 static int run_forward(op_ctx* c, const uint8_t* frames = nullptr, int64_t frame_bytes = 0, int64_t row_stride = 0,
-                       int sh = 0, int sw = 0, float* stages = nullptr) {
+                       int sh = 0, int sw = 0, float* stages = nullptr, int stop_point = -1) {
   c->post_rec.kind = 0;  // the maps a recorded post-process read are overwritten from here on
   Act* B = c->buf;
+  int point = 0;  // probe points passed so far (point 0 is the network input, already in B_X0)
+  if (stop_point == 0) return OP_OK;
+// the launches of probe point `point + 1` are enqueued: stop here when it is the probed one
+#define PROBE_POINT()                 \
+  do {                                \
+    if (++point == stop_point) {      \
+      c->prof_join = false;           \
+      return OP_OK;                   \
+    }                                 \
+  } while (0)
   const size_t stage_px = (size_t)c->gn * (c->gh / 8) * (c->gw / 8);
   auto dump_stage = [&](int s) -> int {
     if (!stages) return OP_OK;
@@ -922,24 +991,34 @@ static int run_forward(op_ctx* c, const uint8_t* frames = nullptr, int64_t frame
     RC(conv1(c, B[B_X0], 0, B[B_C11], 0, c->bb[0], 64, true));
   }
   if (!conv1_done) RC(conv_pool(c, B[B_C11], B[B_C12], B[B_P1], c->bb[1], 64));
+  PROBE_POINT();  // 1
   RC(conv1(c, B[B_P1], 0, B[B_C21], 0, c->bb[2], 128, true));
+  PROBE_POINT();
   RC(conv_pool(c, B[B_C21], B[B_C22], B[B_P2], c->bb[3], 128));
+  PROBE_POINT();
   RC(conv1(c, B[B_P2], 0, B[B_C3A], 0, c->bb[4], 256, true));
+  PROBE_POINT();
   RC(conv1(c, B[B_C3A], 0, B[B_C3B], 0, c->bb[5], 256, true));
+  PROBE_POINT();
   RC(conv1(c, B[B_C3B], 0, B[B_C3A], 0, c->bb[6], 256, true));
+  PROBE_POINT();
   RC(conv_pool(c, B[B_C3A], B[B_C34], B[B_P3], c->bb[7], 256));
+  PROBE_POINT();  // 7
   RC(conv1(c, B[B_P3], 0, B[B_C41], 0, c->bb[8], 512, true));
+  PROBE_POINT();
   RC(conv1(c, B[B_C41], 0, B[B_C42], 0, c->bb[9], 512, true));
+  PROBE_POINT();
   RC(conv1(c, B[B_C42], 0, B[B_C43], 0, c->bb[10], 256, true));
+  PROBE_POINT();
   RC(conv1(c, B[B_C43], 0, B[B_CAT], kCatFeat, c->bb[11], 128, true));
+  PROBE_POINT();  // 11
   // Stages 2-6 run their 7x7 layers on chunk-planar tensors when conv_m16_bf16x3 takes every 7x7
   // launch of this geometry and the fused heads write the stage maps (op_set_stage_layout(ctx, 0)
   // or OP_STAGE_PLANAR=0: the [pixel][channels] buffers): Mconv1..Mconv5 outputs in PA / PB, and the Mconv1 input
   // (the 185-channel concat) in CATP -- the feature slice copied over from CAT once per forward
   // (stage 1's conv5_1 reads it from CAT), every stage's (paf, heat) written there by its head.
   const int sh8 = B[B_BRA].h, sw8 = B[B_BRA].w;
-  const bool planar = c->split && (c->conv_algo == 4 || c->conv_algo == 5) && c->stage_planar && head_fused_on() &&
-                      conv_m16_takes(c->gn, sh8, sw8, 1, 256) && conv_m16_takes(c->gn, sh8, sw8, 2, 128);
+  const bool planar = stages_planar(c);
   if (planar)
     RC(profiled(c, kProfOther, 0.0, 0.0, [&] {
       return launch_split_to_planar(B[B_CAT].p, B[B_CATP].p, c->gn, sh8, sw8, B[B_CAT].pad, B[B_CAT].cs, 128 / 16,
@@ -950,8 +1029,11 @@ static int run_forward(op_ctx* c, const uint8_t* frames = nullptr, int64_t frame
   const Act& cat = B[B_CAT];
   Act s1 = B[B_S1];
   RC(conv1(c, cat, kCatFeat, B[B_BRA], 0, c->s1_first, 256, true));
+  PROBE_POINT();
   RC(conv2(c, B[B_BRA], 0, 128, B[B_BRB], 0, 128, c->s1_g[0][0], c->s1_g[1][0], 128, 128, true));
+  PROBE_POINT();
   RC(conv2(c, B[B_BRB], 0, 128, B[B_BRA], 0, 128, c->s1_g[0][1], c->s1_g[1][1], 128, 128, true));
+  PROBE_POINT();  // 14
   {
     const Act* m32 = (c->split && stages) ? &B[B_MAP32] : nullptr;
     const PackedConv a[2] = {c->s1_g[0][2], c->s1_g[1][2]}, b[2] = {c->s1_last[0], c->s1_last[1]};
@@ -962,6 +1044,7 @@ static int run_forward(op_ctx* c, const uint8_t* frames = nullptr, int64_t frame
       RC(conv2(c, s1, 0, 512, catm, kCatPaf, kCatHeat, c->s1_last[0], c->s1_last[1], 40, 20, false, m32, 0, 40));
     }
     RC(dump_stage(0));
+    PROBE_POINT();  // 15
   }
   // stages 2-6 (CocoPoseNet.py:167-260), on the chunk-planar buffers when `planar` (above)
   Act s6 = B[B_S1];
@@ -970,6 +1053,7 @@ static int run_forward(op_ctx* c, const uint8_t* frames = nullptr, int64_t frame
   const Act& SB = planar ? B[B_PB] : B[B_BRB];
   for (int st = 0; st < 5; ++st) {
     RC(conv1(c, catm, 0, SA, 0, c->st_first[st], 256, true));
+    PROBE_POINT();  // 16 + 6 st
     const Act* src = &SA;
     const Act* dst = &SB;
     c->prof_join = true;  // Mconv2..Mconv5 follow Mconv1 back to back on the stream
@@ -980,6 +1064,7 @@ static int run_forward(op_ctx* c, const uint8_t* frames = nullptr, int64_t frame
         return r;
       }
       std::swap(src, dst);
+      PROBE_POINT();  // restores prof_join
     }
     c->prof_join = false;
     // the last stage also leaves a dense f32 copy (paf at 0, heat at 40) for the post-process
@@ -993,7 +1078,9 @@ static int run_forward(op_ctx* c, const uint8_t* frames = nullptr, int64_t frame
                40));
     }
     RC(dump_stage(st + 1));
+    PROBE_POINT();  // 21 + 6 st
   }
+#undef PROBE_POINT
   return OP_OK;
 }
 
@@ -1620,6 +1707,59 @@ int op_forward(op_ctx* c, const float* x, int32_t n, int32_t h, int32_t w, float
     RC(launch_extract_maps(c->buf[B_CAT].p, n, lh, lw, dpaf, dheat, c->stream));
   OP_HIP_CHECK(hipMemcpyAsync(pafs, dpaf, (size_t)n * 38 * lh * lw * 4, hipMemcpyDeviceToHost, c->stream));
   OP_HIP_CHECK(hipMemcpyAsync(heatmaps, dheat, (size_t)n * 19 * lh * lw * 4, hipMemcpyDeviceToHost, c->stream));
+  OP_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return OP_OK;
+}
+
+int op_forward_probe_info(int32_t point, const char** name, int32_t* channels, int32_t* divisor) {
+  if (point < 0 || point >= op::kProbePoints || !name || !channels || !divisor) return OP_ERR_INVALID;
+  const op::ProbeInfo p = op::probe_info(point);
+  *name = p.name;
+  *channels = p.channels;
+  *divisor = p.div;
+  return OP_OK;
+}
+
+int op_forward_probe(op_ctx* c, const float* x, int32_t n, int32_t h, int32_t w, int32_t point, int32_t frame0,
+                     int32_t nframes, float* out, int64_t out_floats) {
+  using namespace op;
+  RC(check_ctx(c, true));
+  if (!x || !out) {
+    set_error("op_forward_probe: null pointer");
+    return OP_ERR_INVALID;
+  }
+  if (point < 0 || point >= kProbePoints) {
+    set_error("op_forward_probe: point must be 0 .. 45");
+    return OP_ERR_INVALID;
+  }
+  if (h % 8 || w % 8 || h < 16 || w < 16 || n < 1) {
+    set_error("network input must be >= 16 and a multiple of 8");
+    return OP_ERR_INVALID;
+  }
+  if (frame0 < 0 || nframes < 1 || frame0 > n - nframes) {
+    set_error("op_forward_probe: frames [frame0, frame0 + nframes) must lie in [0, n)");
+    return OP_ERR_INVALID;
+  }
+  const ProbeInfo pi = probe_info(point);
+  const int64_t want = (int64_t)nframes * pi.channels * (h / pi.div) * (w / pi.div);
+  if (out_floats != want) {
+    set_error("op_forward_probe: out_floats must be nframes * channels * (h / divisor) * (w / divisor) = " +
+              std::to_string(want));
+    return OP_ERR_INVALID;
+  }
+  RC(ensure_geometry(c, n, h, w));
+  const size_t xin = (size_t)n * 3 * h * w * 4;
+  RC(ensure_scratch(c, xin + 256 + (size_t)want * 4));
+  float* dx = c->d_scratch;
+  float* dout = (float*)((char*)c->d_scratch + (xin + 255) / 256 * 256);
+  OP_HIP_CHECK(hipMemcpyAsync(dx, x, xin, hipMemcpyHostToDevice, c->stream));
+  if (c->split)
+    RC(launch_nchw_to_split16(dx, c->buf[B_X0].p, n, h, w, c->stream));
+  else
+    RC(launch_nchw_to_nhwc8(dx, c->buf[B_X0].p, n, h, w, c->stream));
+  RC(run_forward(c, nullptr, 0, 0, 0, 0, nullptr, point));
+  RC(probe_extract(c, point, frame0, nframes, dout));
+  OP_HIP_CHECK(hipMemcpyAsync(out, dout, (size_t)want * 4, hipMemcpyDeviceToHost, c->stream));
   OP_HIP_CHECK(hipStreamSynchronize(c->stream));
   return OP_OK;
 }

@@ -186,6 +186,26 @@ int op_forward(op_ctx* ctx, const float* x, int32_t n, int32_t h, int32_t w, flo
  * (6, n, 19, h/8, w/8); stage s at index s-1. */
 int op_forward_stages(op_ctx* ctx, const float* x, int32_t n, int32_t h, int32_t w, float* pafs, float* heatmaps);
 
+/* Test aid (no reference counterpart): the forward of op_forward, stopped right after probe point
+ * `point`, and the tensor that point wrote returned as dense f32 (nframes, channels, h/divisor,
+ * w/divisor) for frames [frame0, frame0 + nframes) of the batch; split-stored (bf16x3) values come
+ * back as hi + lo.  Probe points are the launch boundaries of the forward in execution order; a
+ * fused step that runs as separate launches (other conv algos, fp32, OP_HEAD_FUSED=0) is still one
+ * point, after the last of them:
+ *   0 the network input as stored; 1 conv1_1+conv1_2+pool; 2 conv2_1; 3 conv2_2+pool; 4-6 conv3_1 ..
+ *   conv3_3; 7 conv3_4+pool; 8-10 conv4_1, conv4_2, conv4_3_CPM; 11 conv4_4_CPM; 12-14 conv5_1 ..
+ *   conv5_3 (L1 | L2, 256 channels); 15 the stage-1 heads; then for stage s = 2 .. 6 at
+ *   16 + 6 (s - 2) + i: i = 0 .. 4 Mconv1 .. Mconv5 (L1 | L2), i = 5 the heads (Mconv6+Mconv7).
+ * The map points (15, 21, ..., 45) return 185 channels in the order of the reference's F.concat
+ * (models/CocoPoseNet.py:168): paf 38, heat 19, feature 128, read from the buffer the next stage's
+ * Mconv1 reads.  out_floats must equal nframes * channels * (h/divisor) * (w/divisor); a bad point,
+ * frame range or out_floats is OP_ERR_INVALID before anything is launched.  The default forward is
+ * unchanged: no other entry point stops early.
+ * op_forward_probe_info: a point's name, channel count and size divisor (46 points, 0 .. 45). */
+int op_forward_probe_info(int32_t point, const char** name, int32_t* channels, int32_t* divisor);
+int op_forward_probe(op_ctx* ctx, const float* x, int32_t n, int32_t h, int32_t w, int32_t point, int32_t frame0,
+                     int32_t nframes, float* out, int64_t out_floats);
+
 /* F.resize_images (pose_detector.py:501-502; Chainer <= 6 align-corners bilinear): (c,h,w) -> (c,oh,ow). */
 int op_resize_images(op_ctx* ctx, const float* x, int32_t c, int32_t h, int32_t w, int32_t oh, int32_t ow, float* y);
 

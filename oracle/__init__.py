@@ -11,6 +11,10 @@ used as the *checker* for the MI355X path.  Only ``tests/``, ``__graft_entry__.s
 * ``oracle/forward.py``: NumPy restatement of Chainer's CPU forward of models/CocoPoseNet.py.
   Chainer is absent: parity unpinned at that boundary, cross-checked against an independent
   float64 convolution.
+* ``oracle/layer_ref.py``: float64 evaluation of one layer (or fused group) of the forward at chosen
+  pixels, with the 3xBF16 product terms the kernels form, and the sequential-f32 accumulation
+  yardstick; the reference of tests/test_gpu_layerwise.py (our own code, checked by
+  tests/test_layer_ref.py).
 * ``oracle/cvresize.py``: OpenCV INTER_LINEAR restatement.  OpenCV is absent: parity unpinned.
 """
 from . import cvresize, forward, postproc  # noqa: F401

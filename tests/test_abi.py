@@ -64,6 +64,21 @@ def test_layer_table_matches_cocoposenet(lib):
     assert lib.layer_table() == LAYERS
 
 
+def test_probe_table_follows_the_layer_table(lib):
+    """op_forward_probe_info (host only): 46 points; a point's channels are what its last layers write
+    (oracle/layer_ref.py point_spec walks the same launches), 185 at the six map points."""
+    from oracle import layer_ref
+    table = lib.probe_table()
+    co = {name: c for name, _, c, _ in lib.layer_table()}
+    assert len(table) == lib.N_PROBE_POINTS == layer_ref.N_POINTS and table[0] == ("input", 3, 1)
+    for point in range(1, len(table)):
+        src, steps, pooled = layer_ref.point_spec(point)
+        want = sum(co[name] for name, _, _ in steps[-1][0]) + (128 if point in layer_ref.MAP_POINTS else 0)
+        assert table[point][1] == want, (point, table[point])
+        assert table[point][2] == table[src][2] * (2 if pooled else 1), (point, table[point])
+    assert len({t[0] for t in table}) == len(table)
+
+
 def test_forward_flops(lib):
     # SURVEY §6 / Appendix A: 271.9 GFLOP per 368x368 frame, 484.6 at 656x368
     assert abs(lib.forward_flops(368, 368) / 1e9 - 271.868) < 0.01
