@@ -35,6 +35,7 @@ EXPORTED = (
     "op_train_create", "op_train_destroy", "op_train_set_weights", "op_train_get_weights", "op_train_set_hyper",
     "op_train_enable_layer", "op_train_set_grad_scale", "op_train_step",
     "op_make_labels", "op_train_step_poses", "op_train_last_label_ms",
+    "op_train_eval", "op_train_eval_poses", "op_train_get_state", "op_train_set_state",
 )
 ARCH = {"facenet": 1, "handnet": 2}
 MAX_SCALES = 8
@@ -158,6 +159,10 @@ def lib():
         "op_make_labels": ([I32, I32, I32, I32, I32, P, P, P, D, D, P, P, P], ctypes.c_int),
         "op_train_step_poses": ([P, P, P, P, P, D, D, P], ctypes.c_int),
         "op_train_last_label_ms": ([P, P], ctypes.c_int),
+        "op_train_eval": ([P, I32, P, P, P, P, P], ctypes.c_int),
+        "op_train_eval_poses": ([P, I32, P, P, P, P, D, D, P], ctypes.c_int),
+        "op_train_get_state": ([P, P, P, P, P, P], ctypes.c_int),
+        "op_train_set_state": ([P, P, P, P, P, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -914,6 +919,66 @@ class TrainContext(object):
         ms = ctypes.c_double()
         check(lib().op_train_last_label_ms(self.h_, ctypes.byref(ms)), "op_train_last_label_ms")
         return ms.value
+
+    def _eval_frames(self, x):
+        x = np.ascontiguousarray(x, np.float32)
+        if x.ndim != 4 or x.shape[1:] != (3, self.h, self.w) or x.shape[0] < 1:
+            raise ValueError("train eval: x (m,3,h,w) with m >= 1 expected")
+        if x.shape[0] > self.n:
+            raise ValueError("train eval: %d frames, the context holds %d" % (x.shape[0], self.n))
+        return x, x.shape[0]
+
+    def eval(self, x, pafs_t, heatmaps_t, ignore_mask):
+        """The twelve losses ``step`` would report for these m <= n frames (op_train_eval): forward
+        and compute_loss only, nothing of the training state changes."""
+        x, m = self._eval_frames(x)
+        h8, w8 = self.h // 8, self.w // 8
+        pt = np.ascontiguousarray(pafs_t, np.float32)
+        ht = np.ascontiguousarray(heatmaps_t, np.float32)
+        ig = np.ascontiguousarray(ignore_mask, np.uint8)
+        if pt.shape != (m, 38, h8, w8) or ht.shape != (m, 19, h8, w8) or ig.shape != (m, h8, w8):
+            raise ValueError("train eval: shapes (m,3,h,w) (m,38,h/8,w/8) (m,19,h/8,w/8) (m,h/8,w/8) expected")
+        losses = np.zeros(12, np.float64)
+        check(lib().op_train_eval(self.h_, m, ptr(x), ptr(pt), ptr(ht), ptr(ig), ptr(losses)), "op_train_eval")
+        return losses
+
+    def eval_poses(self, x, poses_per_frame, mask=None, heatmap_sigma=7, paf_width=8):
+        """``eval`` with the targets generated on the device from keypoints (op_train_eval_poses),
+        arguments as for ``step_poses`` with m <= n frames."""
+        x, m = self._eval_frames(x)
+        poses, offsets = pack_poses(poses_per_frame, m)
+        mk = pack_mask(mask, m, self.h, self.w)
+        losses = np.zeros(12, np.float64)
+        check(lib().op_train_eval_poses(self.h_, m, ptr(x), ptr(poses), ptr(offsets), ptr(mk), float(heatmap_sigma),
+                                        float(paf_width), ptr(losses)), "op_train_eval_poses")
+        return losses
+
+    def get_state(self):
+        """{layer: dict(mW, vW, mb, vb, t)}: Adam's moments of W and b and the layer's step count."""
+        out = {name: dict(mW=np.empty((co, ci, k, k), np.float32), vW=np.empty((co, ci, k, k), np.float32),
+                          mb=np.empty(co, np.float32), vb=np.empty(co, np.float32))
+               for name, ci, co, k in self.table}
+        ps = [(ctypes.c_void_p * len(self.table))(*[out[t[0]][key].ctypes.data for t in self.table])
+              for key in ("mW", "vW", "mb", "vb")]
+        t = np.zeros(len(self.table), np.int64)
+        check(lib().op_train_get_state(self.h_, ps[0], ps[1], ps[2], ps[3], ptr(t)), "op_train_get_state")
+        for i, row in enumerate(self.table):
+            out[row[0]]["t"] = int(t[i])
+        return out
+
+    def set_state(self, state):
+        """Restore what ``get_state`` returned; after ``set_weights``, which zeroes the state."""
+        arrs = {key: [] for key in ("mW", "vW", "mb", "vb")}
+        for name, ci, co, k in self.table:
+            for key, shape in (("mW", (co, ci, k, k)), ("vW", (co, ci, k, k)), ("mb", (co,)), ("vb", (co,))):
+                a = np.ascontiguousarray(state[name][key], np.float32)
+                if a.shape != shape:
+                    raise ValueError("%s/%s: expected %s, got %s" % (name, key, shape, a.shape))
+                arrs[key].append(a)
+        t = np.ascontiguousarray([int(state[row[0]]["t"]) for row in self.table], np.int64)
+        ps = [(ctypes.c_void_p * len(self.table))(*[a.ctypes.data for a in arrs[key]])
+              for key in ("mW", "vW", "mb", "vb")]
+        check(lib().op_train_set_state(self.h_, ps[0], ps[1], ps[2], ps[3], ptr(t)), "op_train_set_state")
 
 
 def pack_poses(poses_per_frame, n=None):

@@ -195,6 +195,46 @@ __global__ __launch_bounds__(256) void tr_loss(TView Y, int yoff, TView dY, cons
   if (threadIdx.x == 0) part[blockIdx.x] = red[0];
 }
 
+// compute_loss without the backward (op_train_eval): all twelve map tensors in one launch, block
+// (x, y) = 256 elements of tensor y (stage y / 2 + 1; even y: PAFs, odd y: heat maps).  tr_loss's
+// arithmetic, partition and in-block reduction, so a tensor's partials are the ones tr_loss writes;
+// a block past the tensor's elements (the heat tensors have half the PAFs') writes a zero partial.
+// Writes part[y * gridDim.x + x] and nothing else.
+struct EvalMaps {
+  const float* p[12];  // the stage's map buffer
+  int off[12], cs[12], C[12];
+  int h, w, pad;
+};
+__global__ __launch_bounds__(256) void tr_loss_eval(EvalMaps M, const float* __restrict__ tpaf,
+                                                    const float* __restrict__ theat, const uint8_t* __restrict__ ign,
+                                                    int n, double* __restrict__ part) {
+  __shared__ double red[256];
+  const int k = blockIdx.y;
+  const int C = M.C[k];
+  const float* __restrict__ t = (k & 1) ? theat : tpaf;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t hw = (int64_t)M.h * M.w;
+  const int64_t total = (int64_t)n * C * hw;
+  double sq = 0.0;
+  if (i < total) {
+    const int x = (int)(i % M.w);
+    const int yy = (int)((i / M.w) % M.h);
+    const int c = (int)((i / hw) % C);
+    const int f = (int)(i / (hw * C));
+    const int64_t at = (((int64_t)f * (M.h + 2 * M.pad) + yy + M.pad) * (M.w + 2 * M.pad) + x + M.pad) * M.cs[k];
+    const float yv = M.p[k][at + M.off[k] + c];
+    const float d = ign[(int64_t)f * hw + (int64_t)yy * M.w + x] ? 0.0f : yv - t[i];
+    sq = (double)d * (double)d;
+  }
+  red[threadIdx.x] = sq;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[(int64_t)k * gridDim.x + blockIdx.x] = red[0];
+}
+
 // weight gradient partials: workgroup = 64 co x 64 ci of one tap over the pixel range of split z;
 // thread = 4 co x 4 ci; 16-pixel steps staged in LDS.  part[z][tap][co][ci] (co, ci < cop, cip).
 // The centre tap's first ci block also sums the staged G rows: bias partials bpart[z][co].
@@ -522,7 +562,8 @@ int tr_pack_layer(op_train_ctx* c, int l, const TConv& cv) {
   return OP_OK;
 }
 
-int tr_forward(op_train_ctx* c) {
+// the exact-f32 forward over the first n frames of the activation buffers (n <= c->n)
+int tr_forward(op_train_ctx* c, int n) {
   for (size_t k = 0; k < c->convs.size(); ++k) {
     const TConv& cv = c->convs[k];
     const int l = cv.layer;
@@ -536,20 +577,20 @@ int tr_forward(op_train_ctx* c) {
     g[0].cop = c->cop[l];
     g[0].cout_store = cv.store;
     g[1] = g[0];
-    TRC(launch_conv(tshape(c->n, in, out, cv.cin_phys / 8, c->L[l].k, cv.relu), g, c->stream));
+    TRC(launch_conv(tshape(n, in, out, cv.cin_phys / 8, c->L[l].k, cv.relu), g, c->stream));
     // pools after conv1_2, conv2_2, conv3_4; the feature copy after conv4_4_CPM
     const int pool_in = l == 1 ? T_C12 : (l == 3 ? T_C22 : (l == 7 ? T_C34 : -1));
     if (pool_in >= 0) {
       const int pool_out = l == 1 ? T_P1 : (l == 3 ? T_P2 : T_P3);
       const TView& a = c->act[pool_in];
       const TView& o = c->act[pool_out];
-      TRC(launch_maxpool2(a.p, a.pad, o.p, o.pad, c->n, a.h, a.w, a.cs, c->stream));
+      TRC(launch_maxpool2(a.p, a.pad, o.p, o.pad, n, a.h, a.w, a.cs, c->stream));
     }
     if (l == 11)
       for (int s = 1; s < 5; ++s) {
         const TView& d = c->act[T_CAT0 + s];
-        hipLaunchKernelGGL(tr_copy, dim3(nb((int64_t)c->n * d.h * d.w * 128)), dim3(256), 0, c->stream, d, kCatFeat,
-                           c->act[T_CAT0], kCatFeat, c->n, 128);
+        hipLaunchKernelGGL(tr_copy, dim3(nb((int64_t)n * d.h * d.w * 128)), dim3(256), 0, c->stream, d, kCatFeat,
+                           c->act[T_CAT0], kCatFeat, n, 128);
       }
   }
   OP_HIP_CHECK(hipGetLastError());
@@ -674,7 +715,7 @@ int tr_step_core(op_train_ctx* c, double* losses) {
   const size_t xin = step_sizes(c).xin, tp = step_sizes(c).tp;
   // preprocess happens on the host side of the reference (:80-86): x is the network input
   hipLaunchKernelGGL(tr_input, dim3(nb((int64_t)xin)), dim3(256), 0, c->stream, c->d_x, c->act[T_X0], n);
-  TRC(tr_forward(c));
+  TRC(tr_forward(c, n));
   // gradients start at zero (halos too: the input-gradient convs read them)
   OP_HIP_CHECK(hipMemsetAsync((float*)c->arena + c->grad_off, 0, c->grad_off * 4, c->stream));
   // (no per-step gradient clearing: every enabled layer's tr_wreduce / tr_breduce assigns its whole
@@ -730,6 +771,88 @@ int tr_step_core(op_train_ctx* c, double* losses) {
       for (size_t i = 0; i < nblocks; ++i) s += part[k * nblocks + i];
       losses[k] = s / (double)((int64_t)n * m.C * h8 * w8);
     }
+  return OP_OK;
+}
+
+// Forward + compute_loss over the first m frames of what the stream has put into d_x, d_t (PAF
+// targets at d_t, heat targets at d_t + step_sizes().tp, both (m, C, h8, w8)) and d_ign: no
+// gradient buffer, weight, Adam or label-event state is touched; waits for the stream.  Frames
+// m..n-1 of the activation buffers keep what the last call left there and are not read.
+int tr_eval_core(op_train_ctx* c, int m, double* losses) {
+  const int h8 = c->h / 8, w8 = c->w / 8;
+  hipLaunchKernelGGL(tr_input, dim3(nb((int64_t)m * 3 * c->h * c->w)), dim3(256), 0, c->stream, c->d_x, c->act[T_X0],
+                     m);
+  TRC(tr_forward(c, m));
+  const size_t nblocks = nb((int64_t)m * 38 * h8 * w8);  // tr_step_core's partition (the PAF tensors' blocks)
+  if (c->lpart_n < 12 * nblocks) {
+    OP_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (c->lpart) OP_HIP_CHECK(hipFree(c->lpart));
+    c->lpart = nullptr;
+    c->lpart_n = 0;
+    OP_HIP_CHECK(hipMalloc(&c->lpart, 12 * nblocks * sizeof(double)));
+    c->lpart_n = 12 * nblocks;
+  }
+  EvalMaps M;
+  for (int k = 0; k < 12; ++k) {
+    const MapT t = stage_map(k / 2 + 1, k % 2 == 0);
+    M.p[k] = c->act[t.buf].p;
+    M.off[k] = t.off;
+    M.cs[k] = c->act[t.buf].cs;
+    M.C[k] = t.C;
+  }
+  M.h = h8;
+  M.w = w8;
+  M.pad = kPad;
+  hipLaunchKernelGGL(tr_loss_eval, dim3((unsigned)nblocks, 12), dim3(256), 0, c->stream, M, c->d_t,
+                     c->d_t + step_sizes(c).tp, c->d_ign, m, c->lpart);
+  OP_AFTER_LAUNCH("tr_loss_eval", c->stream);
+  OP_HIP_CHECK(hipGetLastError());
+  std::vector<double> part(12 * nblocks);
+  OP_HIP_CHECK(hipMemcpyAsync(part.data(), c->lpart, part.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  OP_HIP_CHECK(hipStreamSynchronize(c->stream));
+  for (int k = 0; k < 12; ++k) {  // tr_step_core's summation order and divide
+    const MapT t = stage_map(k / 2 + 1, k % 2 == 0);
+    double s = 0.0;
+    for (size_t i = 0; i < nblocks; ++i) s += part[k * nblocks + i];
+    losses[k] = s / (double)((int64_t)m * t.C * h8 * w8);
+  }
+  return OP_OK;
+}
+
+// The label buffers of op_train_step_poses / op_train_eval_poses: the index and the full-resolution
+// mask sized for the context's n frames at the first such call (lh holds `frames` <= n of them),
+// the record buffer grown on demand, and the step's label events.
+int tr_label_buffers(op_train_ctx* c, const LabelHost& lh, int frames) {
+  if (!c->d_idx) {
+    OP_HIP_CHECK(hipMalloc(&c->d_idx, lh.idx.size() / frames * c->n * sizeof(int32_t)));
+    OP_HIP_CHECK(hipMalloc(&c->d_mask, (size_t)c->n * c->h * c->w));
+    OP_HIP_CHECK(hipEventCreate(&c->ev_lab[0]));
+    OP_HIP_CHECK(hipEventCreate(&c->ev_lab[1]));
+  }
+  if (lh.rec.size() > c->rec_cap) {  // (no step is in flight: every step ends with a stream wait)
+    if (c->d_rec) OP_HIP_CHECK(hipFree(c->d_rec));
+    c->d_rec = nullptr;
+    c->rec_cap = 0;
+    OP_HIP_CHECK(hipMalloc(&c->d_rec, 2 * lh.rec.size() * sizeof(double)));
+    c->rec_cap = 2 * lh.rec.size();
+  }
+  return OP_OK;
+}
+
+int tr_eval_check(op_train_ctx* c, const char* who, int32_t m, const void* x, double* losses) {
+  TRC(tr_check(c));
+  if (m < 1 || m > c->n) {
+    set_error(std::string(who) + ": 1 <= m <= n (" + std::to_string(c->n) + ") expected, got " + std::to_string(m));
+    return OP_ERR_INVALID;
+  }
+  if (!c->have_weights) {
+    set_error(std::string(who) + ": weights not set");
+    return OP_ERR_STATE;
+  }
+  if (!x || !losses) {
+    set_error(std::string(who) + ": null pointer");
+    return OP_ERR_INVALID;
+  }
   return OP_OK;
 }
 
@@ -942,19 +1065,7 @@ int op_train_step_poses(op_train_ctx* c, const float* x, const double* poses, co
   const StepSizes z = step_sizes(c);
   const size_t mbytes = (size_t)c->n * c->h * c->w;
   TRC(tr_step_buffers(c));
-  if (!c->d_idx) {
-    OP_HIP_CHECK(hipMalloc(&c->d_idx, lh.idx.size() * sizeof(int32_t)));
-    OP_HIP_CHECK(hipMalloc(&c->d_mask, mbytes));
-    OP_HIP_CHECK(hipEventCreate(&c->ev_lab[0]));
-    OP_HIP_CHECK(hipEventCreate(&c->ev_lab[1]));
-  }
-  if (lh.rec.size() > c->rec_cap) {  // (no step is in flight: every step ends with a stream wait)
-    if (c->d_rec) OP_HIP_CHECK(hipFree(c->d_rec));
-    c->d_rec = nullptr;
-    c->rec_cap = 0;
-    OP_HIP_CHECK(hipMalloc(&c->d_rec, 2 * lh.rec.size() * sizeof(double)));
-    c->rec_cap = 2 * lh.rec.size();
-  }
+  TRC(tr_label_buffers(c, lh, c->n));
   OP_HIP_CHECK(hipMemcpyAsync(c->d_x, x, z.xin * 4, hipMemcpyHostToDevice, c->stream));
   c->lab_timed = false;
   OP_HIP_CHECK(hipEventRecord(c->ev_lab[0], c->stream));
@@ -978,6 +1089,81 @@ int op_train_last_label_ms(op_train_ctx* c, double* ms) {
   float t = 0.0f;
   OP_HIP_CHECK(hipEventElapsedTime(&t, c->ev_lab[0], c->ev_lab[1]));
   *ms = (double)t;
+  return OP_OK;
+}
+
+int op_train_eval(op_train_ctx* c, int32_t m, const float* x, const float* pafs_t, const float* heat_t,
+                  const uint8_t* ignore, double* losses) {
+  TRC(tr_eval_check(c, "op_train_eval", m, x, losses));
+  if (!pafs_t || !heat_t || !ignore) {
+    set_error("op_train_eval: null pointer");
+    return OP_ERR_INVALID;
+  }
+  const size_t hw8 = (size_t)(c->h / 8) * (c->w / 8);
+  TRC(tr_step_buffers(c));
+  OP_HIP_CHECK(hipMemcpyAsync(c->d_x, x, (size_t)m * 3 * c->h * c->w * 4, hipMemcpyHostToDevice, c->stream));
+  OP_HIP_CHECK(hipMemcpyAsync(c->d_t, pafs_t, m * 38 * hw8 * 4, hipMemcpyHostToDevice, c->stream));
+  OP_HIP_CHECK(hipMemcpyAsync(c->d_t + step_sizes(c).tp, heat_t, m * 19 * hw8 * 4, hipMemcpyHostToDevice, c->stream));
+  OP_HIP_CHECK(hipMemcpyAsync(c->d_ign, ignore, m * hw8, hipMemcpyHostToDevice, c->stream));
+  return tr_eval_core(c, m, losses);
+}
+
+int op_train_eval_poses(op_train_ctx* c, int32_t m, const float* x, const double* poses, const int32_t* pose_offsets,
+                        const uint8_t* mask, double heatmap_sigma, double paf_width, double* losses) {
+  TRC(tr_eval_check(c, "op_train_eval_poses", m, x, losses));
+  LabelHost lh;  // (alive until the stream has been waited for: the uploads below read it)
+  TRC(labels_pack("op_train_eval_poses", m, c->h, c->w, 8, poses, pose_offsets, heatmap_sigma, paf_width, &lh));
+  const size_t mbytes = (size_t)m * c->h * c->w;
+  TRC(tr_step_buffers(c));
+  TRC(tr_label_buffers(c, lh, m));
+  // (the label events and op_train_last_label_ms belong to op_train_step_poses: not recorded here)
+  OP_HIP_CHECK(hipMemcpyAsync(c->d_x, x, (size_t)m * 3 * c->h * c->w * 4, hipMemcpyHostToDevice, c->stream));
+  OP_HIP_CHECK(hipMemcpyAsync(c->d_rec, lh.rec.data(), lh.rec.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  OP_HIP_CHECK(hipMemcpyAsync(c->d_idx, lh.idx.data(), lh.idx.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  if (mask) OP_HIP_CHECK(hipMemcpyAsync(c->d_mask, mask, mbytes, hipMemcpyHostToDevice, c->stream));
+  TRC(launch_make_labels(lh, c->d_rec, c->d_idx, mask ? c->d_mask : nullptr, m, c->h, c->w, 8, heatmap_sigma,
+                         paf_width, c->d_t, c->d_t + step_sizes(c).tp, c->d_ign, c->stream));
+  return tr_eval_core(c, m, losses);
+}
+
+int op_train_get_state(op_train_ctx* c, float* const* mW, float* const* vW, float* const* mb, float* const* vb,
+                       int64_t* t) {
+  TRC(tr_check(c));
+  OP_HIP_CHECK(hipStreamSynchronize(c->stream));
+  for (int l = 0; l < kNL; ++l) {
+    const TLayer& d = c->L[l];
+    const size_t nw = (size_t)d.co * d.ci * d.k * d.k * 4;
+    if (mW && mW[l]) OP_HIP_CHECK(hipMemcpy(mW[l], c->mW[l], nw, hipMemcpyDeviceToHost));
+    if (vW && vW[l]) OP_HIP_CHECK(hipMemcpy(vW[l], c->vW[l], nw, hipMemcpyDeviceToHost));
+    if (mb && mb[l]) OP_HIP_CHECK(hipMemcpy(mb[l], c->mb[l], d.co * 4, hipMemcpyDeviceToHost));
+    if (vb && vb[l]) OP_HIP_CHECK(hipMemcpy(vb[l], c->vb[l], d.co * 4, hipMemcpyDeviceToHost));
+    if (t) t[l] = c->t_step[l];
+  }
+  return OP_OK;
+}
+
+int op_train_set_state(op_train_ctx* c, const float* const* mW, const float* const* vW, const float* const* mb,
+                       const float* const* vb, const int64_t* t) {
+  TRC(tr_check(c));
+  if (!mW || !vW || !mb || !vb || !t) {
+    set_error("op_train_set_state: null pointer");
+    return OP_ERR_INVALID;
+  }
+  for (int l = 0; l < kNL; ++l)  // validated before anything is written
+    if (!mW[l] || !vW[l] || !mb[l] || !vb[l] || t[l] < 0) {
+      set_error("op_train_set_state: missing state or negative step count for layer " + c->L[l].name);
+      return OP_ERR_INVALID;
+    }
+  OP_HIP_CHECK(hipStreamSynchronize(c->stream));
+  for (int l = 0; l < kNL; ++l) {
+    const TLayer& d = c->L[l];
+    const size_t nw = (size_t)d.co * d.ci * d.k * d.k * 4;
+    OP_HIP_CHECK(hipMemcpy(c->mW[l], mW[l], nw, hipMemcpyHostToDevice));
+    OP_HIP_CHECK(hipMemcpy(c->vW[l], vW[l], nw, hipMemcpyHostToDevice));
+    OP_HIP_CHECK(hipMemcpy(c->mb[l], mb[l], d.co * 4, hipMemcpyHostToDevice));
+    OP_HIP_CHECK(hipMemcpy(c->vb[l], vb[l], d.co * 4, hipMemcpyHostToDevice));
+    c->t_step[l] = t[l];
+  }
   return OP_OK;
 }
 

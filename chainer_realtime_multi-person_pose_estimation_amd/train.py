@@ -18,6 +18,13 @@ network: ``synthetic_batch`` stands in with seeded images and COCO-like maps of 
 (people, 18, 3) poses as parse_coco_annotation makes them, and ``Updater.update_poses`` has the
 device generate the targets from them inside the step (labels.py, op_train_step_poses).
 
+``Validator`` is the reference's (:129-159): every ``--val-interval`` iterations a fixed held-out set
+is scored with ``Updater.evaluate`` (op_train_eval: forward + compute_loss only, the training state
+is left alone) and ``val/loss``, ``val/paf``, ``val/heat`` join that log entry; at the same points
+``Updater.save_snapshot`` writes ``snapshot_iter_N.npz`` (weights, Adam moments, per-layer step
+counts, iteration, alpha, frozen layers: extensions.snapshot(), :255) beside ``model_iter_N.npz``, and
+``--resume-from FILE`` (the reference's ``--resume FILE``, :265-266) continues from one bit for bit.
+
     python -m chainer_realtime_multi-person_pose_estimation_amd.train --batchsize 4 --iteration 10
 """
 import argparse
@@ -84,7 +91,9 @@ class Updater(object):
     def __init__(self, n, h=368, w=368, model=None, device=0, alpha=1e-4, beta1=0.9, beta2=0.999, eps=1e-8,
                  resume=False, ctx=None):
         self.ctx = ctx if ctx is not None else _lib.TrainContext(n, h, w, device)
+        self.n = int(n)
         self.names = [t[0] for t in self.ctx.table]
+        self.enabled = {name: True for name in self.names}  # the device's flags, tracked for the snapshot
         self.iteration = 0
         self.alpha, self.beta1, self.beta2, self.eps = alpha, beta1, beta2, eps
         self.hooks = []
@@ -101,9 +110,11 @@ class Updater(object):
 
     def enable_update(self, name):
         self.ctx.enable(self.names.index(name), True)
+        self.enabled[name] = True
 
     def disable_update(self, name):
         self.ctx.enable(self.names.index(name), False)
+        self.enabled[name] = False
 
     def _schedule(self):
         if self.iteration == 2000:
@@ -130,15 +141,107 @@ class Updater(object):
 
     def _log(self, losses):
         self.iteration += 1
+        return self._losses(losses)
+
+    @staticmethod
+    def _losses(losses):
         paf_log = [float(v) for v in losses[0::2]]
         heat_log = [float(v) for v in losses[1::2]]
         return sum(paf_log) + sum(heat_log), paf_log, heat_log
+
+    def evaluate(self, batch):
+        """``update``'s losses for a batch of m <= n frames without the update (the body of the
+        reference's Validator.evaluate loop, :146-157): no schedule step, no backward, no Adam, the
+        iteration count stays.  Same return value as ``update``."""
+        imgs, pafs, heatmaps, ignore_mask = batch
+        return self._losses(self.ctx.eval(preprocess(imgs), pafs, heatmaps, ignore_mask))
+
+    def evaluate_poses(self, imgs, poses_per_frame, mask=None):
+        """``evaluate`` with the targets made on the device, arguments as for ``update_poses``."""
+        return self._losses(self.ctx.eval_poses(preprocess(imgs), poses_per_frame, mask,
+                                                train_params["heatmap_sigma"], train_params["paf_sigma"]))
 
     def weights(self):
         return self.ctx.get()
 
     def grads(self):
         return self.ctx.get(grads=True)
+
+    def save_snapshot(self, path):
+        """The trainer's state in one npz (no pickle), keys laid out after Chainer's trainer snapshot
+        (extensions.snapshot(), :255; modelled on it, not verified against Chainer):
+        ``updater/model:main/<layer>/{W,b}``, ``updater/optimizer:main/<layer>/{W,b}/{m,v}``,
+        ``updater/optimizer:main/<layer>/t``, ``updater/iteration``, ``updater/alpha`` and
+        ``updater/enabled`` (u8 per layer, table order).  ``weights.load_npz`` reads the model out of
+        it, so the file also serves as ``--initmodel``."""
+        flat = {}
+        W, S = self.ctx.get(), self.ctx.get_state()
+        for name in self.names:
+            flat["updater/model:main/%s/W" % name], flat["updater/model:main/%s/b" % name] = W[name]
+            opt = "updater/optimizer:main/%s/" % name
+            flat[opt + "W/m"], flat[opt + "W/v"] = S[name]["mW"], S[name]["vW"]
+            flat[opt + "b/m"], flat[opt + "b/v"] = S[name]["mb"], S[name]["vb"]
+            flat[opt + "t"] = np.int64(S[name]["t"])
+        flat["updater/iteration"] = np.int64(self.iteration)
+        flat["updater/alpha"] = np.float64(self.alpha)
+        flat["updater/enabled"] = np.array([self.enabled[name] for name in self.names], np.uint8)
+        with open(path, "wb") as f:  # (np.savez would append .npz to a bare path)
+            np.savez(f, **flat)
+
+    def load_snapshot(self, path):
+        """``--resume FILE`` (:265-266): weights, then the Adam state (set_weights zeroes it), the
+        iteration, alpha and the enabled flags; the hooks are applied again.  The schedule goes on
+        as if the run had not stopped."""
+        with np.load(path, allow_pickle=False) as z:
+            W, S = {}, {}
+            for name in self.names:
+                W[name] = (z["updater/model:main/%s/W" % name], z["updater/model:main/%s/b" % name])
+                opt = "updater/optimizer:main/%s/" % name
+                S[name] = dict(mW=z[opt + "W/m"], vW=z[opt + "W/v"], mb=z[opt + "b/m"], vb=z[opt + "b/v"],
+                               t=int(z[opt + "t"]))
+            iteration, alpha = int(z["updater/iteration"]), float(z["updater/alpha"])
+            enabled = np.asarray(z["updater/enabled"])
+        if enabled.shape != (len(self.names),):
+            raise ValueError("%s: updater/enabled has %s entries, %d layers expected" % (path, enabled.shape,
+                                                                                       len(self.names)))
+        self.ctx.set_weights(W)
+        self.ctx.set_state(S)
+        self.iteration = iteration
+        self.alpha = alpha
+        self.ctx.set_hyper(self.alpha, self.beta1, self.beta2, self.eps)
+        for name, on in zip(self.names, enabled):
+            (self.enable_update if on else self.disable_update)(name)
+        for hook in self.hooks:
+            hook(self)
+
+
+class Validator(object):
+    """The reference's Validator (:129-159) over a fixed list of held-out batches: ``evaluate()``
+    scores the updater's current weights on each batch (``Updater.evaluate``, or ``evaluate_poses``
+    with ``poses=True`` and batches of (imgs, poses_per_frame, mask)) and returns the plain mean over
+    batches of the per-batch ``val/loss``, ``val/paf`` and ``val/heat`` (DictSummary.compute_mean: a
+    shorter last batch is one observation like any other).  A batch may hold fewer frames than the
+    updater's n but not more: it is never split, which would change the mean."""
+
+    def __init__(self, updater, batches, poses=False):
+        self.updater = updater
+        self.batches = list(batches)
+        self.poses = poses
+
+    def evaluate(self):
+        if not self.batches:
+            raise ValueError("Validator: no batches")
+        for batch in self.batches:
+            if len(batch[0]) > self.updater.n:
+                raise ValueError("Validator: a batch of %d frames, the updater holds %d" % (len(batch[0]),
+                                                                                          self.updater.n))
+        obs = {"val/loss": [], "val/paf": [], "val/heat": []}
+        for batch in self.batches:
+            loss, pl, hl = self.updater.evaluate_poses(*batch) if self.poses else self.updater.evaluate(batch)
+            obs["val/loss"].append(loss)
+            obs["val/paf"].append(sum(pl))
+            obs["val/heat"].append(sum(hl))
+        return {k: sum(v) / len(v) for k, v in obs.items()}
 
 
 def synthetic_batch(rng, n, h, w, people=3):
@@ -191,7 +294,35 @@ def synthetic_poses(rng, n, h, w, people=4):
     return out
 
 
-def main(argv=None):
+def validation_batches(seed, samples, valbatchsize, insize, data="maps", people=4):
+    """The held-out set of the CLI: ``samples`` synthetic frames in batches of ``valbatchsize`` (the
+    last one shorter), drawn once from a stream seeded apart from the training stream's."""
+    rng = np.random.default_rng([int(seed), 1])
+    out = []
+    for start in range(0, samples, valbatchsize):
+        m = min(valbatchsize, samples - start)
+        if data == "poses":
+            imgs = rng.integers(0, 256, (m, insize, insize, 3), dtype=np.uint8)
+            out.append((imgs, synthetic_poses(rng, m, insize, insize, people),
+                        rng.random((m, insize, insize)) < 0.0005))
+        else:
+            out.append(synthetic_batch(rng, m, insize, insize))
+    return out
+
+
+def _mean_entry(observations):
+    """LogReport: one entry per interval, every key's mean over the iterations that reported it."""
+    keys = []
+    for o in observations:
+        keys += [k for k in o if k not in keys and k != "iteration"]
+    entry = {"iteration": observations[-1]["iteration"]}
+    for k in keys:
+        vals = [o[k] for o in observations if k in o]
+        entry[k] = sum(vals) / len(vals)
+    return entry
+
+
+def main(argv=None, ctx=None):
     ap = argparse.ArgumentParser(description="Train pose estimation (MI355X, synthetic data)")
     ap.add_argument("--arch", "-a", choices=["posenet"], default="posenet")
     ap.add_argument("--batchsize", "-B", type=int, default=10)
@@ -205,12 +336,36 @@ def main(argv=None):
     ap.add_argument("--data", choices=["maps", "poses"], default="maps",
                     help="maps: host-made synthetic target maps; poses: synthetic keypoints, targets made on the device")
     ap.add_argument("--people", type=int, default=4, help="people per frame (--data poses)")
+    ap.add_argument("--resume-from", metavar="FILE", help="continue from a snapshot_iter_N.npz (the reference's "
+                    "--resume FILE): weights, Adam state, iteration, alpha and frozen layers")
+    ap.add_argument("--valbatchsize", "-b", type=int, default=4, help="validation minibatch size (<= --batchsize)")
+    ap.add_argument("--val_samples", type=int, default=100, help="number of validation samples")
+    ap.add_argument("--val-interval", type=int, default=1000,
+                    help="validate and write snapshot_iter_N.npz + model_iter_N.npz every this many iterations")
+    ap.add_argument("--log-interval", type=int, default=1,
+                    help="one log entry per this many iterations, holding the means over them")
+    ap.add_argument("--test", action="store_true", help="validation interval 10, log interval 1")
     args = ap.parse_args(argv)
+    if args.test:
+        args.val_interval, args.log_interval = 10, 1
+    if args.val_interval < 1 or args.log_interval < 1 or args.valbatchsize < 1 or args.val_samples < 1:
+        ap.error("--val-interval, --log-interval, --valbatchsize and --val_samples must be positive")
     model = _weights.load_npz(args.initmodel) if args.initmodel else _weights.random_weights(args.seed)
-    up = Updater(args.batchsize, args.insize, args.insize, model=model, device=max(args.gpu, 0), resume=args.resume)
-    rng = np.random.default_rng(args.seed)
+    up = Updater(args.batchsize, args.insize, args.insize, model=model, device=max(args.gpu, 0), resume=args.resume,
+                 ctx=ctx)
+    if args.resume_from:
+        up.load_snapshot(args.resume_from)
+    last = up.iteration + args.iteration
+    validator = None
+    if last // args.val_interval > up.iteration // args.val_interval:  # a validation point lies ahead
+        if args.valbatchsize > args.batchsize:
+            ap.error("--valbatchsize must not exceed --batchsize (validation runs in the training context)")
+        validator = Validator(up, validation_batches(args.seed, args.val_samples, args.valbatchsize, args.insize,
+                                                     args.data, args.people), poses=args.data == "poses")
+    # (a resumed run draws fresh synthetic batches instead of replaying the stream from its start)
+    rng = np.random.default_rng([args.seed, 2, up.iteration] if args.resume_from else args.seed)
     os.makedirs(args.out, exist_ok=True)
-    log = []
+    log, pending, saved = [], [], None
     for it in range(args.iteration):
         if args.data == "poses":
             imgs = rng.integers(0, 256, (args.batchsize, args.insize, args.insize, 3), dtype=np.uint8)
@@ -228,13 +383,27 @@ def main(argv=None):
             loss, pl, hl = up.update(batch)
             dt = time.perf_counter() - t0
             extra, note = {}, ""
-        log.append(dict({"iteration": up.iteration, "main/loss": loss, "main/paf": sum(pl), "main/heat": sum(hl),
-                         "elapsed_s": dt}, **extra))
+        pending.append(dict({"iteration": up.iteration, "main/loss": loss, "main/paf": sum(pl), "main/heat": sum(hl),
+                             "elapsed_s": dt}, **extra))
         print("iter %d loss %.6f paf %.6f heat %.6f (%.1f ms%s)" % (up.iteration, loss, sum(pl), sum(hl), dt * 1e3,
                                                                     note), flush=True)
+        if up.iteration % args.val_interval == 0:  # Validator, snapshot() and snapshot_object (:252-257)
+            val = validator.evaluate()
+            pending[-1].update(val)
+            print("iter %d val/loss %.6f val/paf %.6f val/heat %.6f" % (up.iteration, val["val/loss"], val["val/paf"],
+                                                                       val["val/heat"]), flush=True)
+            up.save_snapshot(os.path.join(args.out, "snapshot_iter_%d.npz" % up.iteration))
+            _weights.save_npz(os.path.join(args.out, "model_iter_%d.npz" % up.iteration), up.weights())
+            saved = up.iteration
+        if up.iteration % args.log_interval == 0:
+            log.append(pending[0] if args.log_interval == 1 else _mean_entry(pending))
+            pending = []
+    if pending:  # the iterations after the last full log interval
+        log.append(_mean_entry(pending))
     with open(os.path.join(args.out, "log"), "w") as f:
         json.dump(log, f, indent=1)
-    _weights.save_npz(os.path.join(args.out, "model_iter_%d.npz" % up.iteration), up.weights())
+    if saved != up.iteration:
+        _weights.save_npz(os.path.join(args.out, "model_iter_%d.npz" % up.iteration), up.weights())
     return 0
 
 

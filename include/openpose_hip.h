@@ -11,6 +11,11 @@
  * Conventions: plain pointers + sizes; all host pointers, row-major, C-contiguous.
  * Every function returns an int status (OP_OK = 0); op_last_error() describes the last failure
  * on the calling thread.  A context is single-threaded and owns one HIP stream on one device.
+ *
+ * The training ABI grew by four calls (op_train_eval, op_train_eval_poses, op_train_get_state,
+ * op_train_set_state: validation passes and snapshot / resume); nothing existing changed.  This
+ * header is part of the digest op_build_info reports, so a library built before them reports
+ * another digest.
  */
 #ifndef OPENPOSE_HIP_H
 #define OPENPOSE_HIP_H
@@ -492,6 +497,33 @@ int op_train_step_poses(op_train_ctx* ctx, const float* x, const double* poses, 
 /* Device time (ms, stream events) of the label part of the last op_train_step_poses: the uploads of
  * the pose records and the mask plus the label kernel.  OP_ERR_STATE before the first such step. */
 int op_train_last_label_ms(op_train_ctx* ctx, double* ms);
+
+/* ---- Validation (Validator.evaluate, train_coco_pose_estimation.py:129-159) ----
+ * The forward and compute_loss of op_train_step over the first m frames of the context (1 <= m <= n,
+ * else OP_ERR_INVALID; OP_ERR_STATE before op_train_set_weights): arrays as for op_train_step with m
+ * in place of n.  No backward and no update: weights, Adam state, step counters, enabled flags,
+ * gradient scales, the gradients op_train_get_weights reports and op_train_last_label_ms are all
+ * left as they were.  The loss arithmetic is op_train_step's (same blocks, same reduction order), so
+ * with m == n the twelve losses equal, bit for bit, the ones a following op_train_step returns for
+ * the same batch. */
+int op_train_eval(op_train_ctx* ctx, int32_t m, const float* x, const float* pafs_t, const float* heat_t,
+                  const uint8_t* ignore, double* losses /* 12 */);
+/* op_train_eval with the targets generated on the device as in op_train_step_poses (pose_offsets has
+ * m + 1 entries, mask (m, h, w) or null). */
+int op_train_eval_poses(op_train_ctx* ctx, int32_t m, const float* x, const double* poses,
+                        const int32_t* pose_offsets, const uint8_t* mask, double heatmap_sigma, double paf_width,
+                        double* losses /* 12 */);
+
+/* ---- Optimizer state (extensions.snapshot() / --resume FILE, :255, :265-266) ----
+ * Adam's first and second moments of every layer's W and b and the per-layer step counts t (a layer
+ * counts only the steps it was enabled in), arrays of 92 pointers / values in op_layer_info order.
+ * get waits for the stream; a null array or null entry is skipped.  set needs every pointer and
+ * t[l] >= 0 (else OP_ERR_INVALID, nothing written).  op_train_set_weights zeroes this state, so a
+ * restore calls op_train_set_weights first and op_train_set_state after it. */
+int op_train_get_state(op_train_ctx* ctx, float* const* mW, float* const* vW, float* const* mb, float* const* vb,
+                       int64_t* t /* 92 */);
+int op_train_set_state(op_train_ctx* ctx, const float* const* mW, const float* const* vW, const float* const* mb,
+                       const float* const* vb, const int64_t* t /* 92 */);
 
 #ifdef __cplusplus
 }
