@@ -1,5 +1,5 @@
 // Host-side weight packing and SciPy Gaussian taps shared by the CocoPoseNet runtime
-// (runtime.hip) and the FaceNet / HandNet detectors (cpm.hip).
+// (weights.hip, runtime.hip) and the FaceNet / HandNet detectors (cpm.hip).
 #pragma once
 #include <stdint.h>
 #include <string.h>

@@ -1,8 +1,14 @@
-// Kernels of the multi-scale path PoseDetector.detect_precise (pose_detector.py:433-482):
+// Kernels, host driver and C ABI of the multi-scale path PoseDetector.detect_precise (pose_detector.py:433-482):
 // cv2.resize(INTER_CUBIC) of the frame fused with pad_image + preprocess into the network input,
 // and the cubic resizes of the last-stage maps (to the padded size, crop, to the original size)
 // fused with the running sum over scales and the final division by the scale count.
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
 #include "common.hpp"
+#include "ctx.hpp"
 #include "cvcubic.hpp"
 
 namespace op {
@@ -965,3 +971,331 @@ int launch_resize_cubic_u8(const uint8_t* src, int64_t sstride, int32_t sh, int3
 }
 
 }  // namespace op
+
+// ---- host driver and C ABI of the multi-scale path ----
+extern "C" {
+
+// detect_precise (pose_detector.py:433-482).  Sizes follow the reference's Python arithmetic:
+// multiplier = scale * inference_img_size / min(h, w) and math.ceil(w * multiplier) in f64.
+// detect_precise (pose_detector.py:433-482) for the n frames (h x w, contiguous) at c->d_frames:
+// per scale one batched forward of the n frames (cubic resize + pad + normalise per frame), then
+// per frame the cubic map resizes into its running mean (psum: [frame][38 paf | 19 heat][h][w]),
+// then the full-resolution post-process of all n frames (results at frame index f).
+static int precise_run(op_ctx* c, int n, int h, int w, int* net_w, int* net_h, bool staged) {
+  const int ds = c->prm.downscale;
+  const int ns = c->prm.n_scales;
+  int rws[OP_MAX_SCALES], rhs[OP_MAX_SCALES], pws[OP_MAX_SCALES], phs[OP_MAX_SCALES];
+  size_t mid_off[OP_MAX_SCALES + 1] = {0};  // floats: every scale's padded-size maps of every frame
+  for (int k = 0; k < ns; ++k) {
+    const double m = c->prm.inference_scales[k] * (double)c->prm.inference_img_size / (double)(h < w ? h : w);
+    rws[k] = (int)std::ceil((double)w * m);
+    rhs[k] = (int)std::ceil((double)h * m);
+    pws[k] = rws[k] + (ds - rws[k] % ds) % ds;
+    phs[k] = rhs[k] + (ds - rhs[k] % ds) % ds;
+    if (rws[k] < 1 || rhs[k] < 1 || phs[k] < 16 || pws[k] < 16) {
+      set_error("detect_precise: a scale gives a network input below 16 x 16");
+      return OP_ERR_INVALID;
+    }
+    mid_off[k + 1] = mid_off[k] + (size_t)n * phs[k] * pws[k] * (OP_N_PAF + OP_N_HEAT);
+  }
+  const int64_t fplanes = (int64_t)(OP_N_PAF + OP_N_HEAT) * h * w;  // floats per frame of psum
+  // round 4 experiment, OFF by default: both map resizes and the scale mean in one pass from each
+  // scale's last-stage maps (copied planar into d_pmid at low_off[k]) -- bit-identical, but it
+  // recomputes each tile's crop halo and makes ~4.5x the VALU instructions of the two-pass path,
+  // which is VALU/issue-bound rather than HBM-bound: 12.5 vs 11.3 ms per 16 1280x720 frames
+  // (SQ_INSTS_VALU, profiles/r04/c4_fused_cubic_not_kept.md).  OP_CUBIC_FUSED=1 selects it.
+  CubicFusedArgs fa{};
+  size_t low_off[OP_MAX_SCALES + 1] = {0};
+  fa.ns = ns;
+  for (int k = 0; k < ns; ++k) {
+    fa.lh[k] = phs[k] / ds;
+    fa.lw[k] = pws[k] / ds;
+    fa.pw[k] = pws[k];
+    fa.rh[k] = rhs[k];
+    fa.rw[k] = rws[k];
+    fa.s1x[k] = 1.0 / ((double)pws[k] / (double)fa.lw[k]);  // cv_cubic_scale (cvcubic.hpp)
+    fa.s1y[k] = 1.0 / ((double)phs[k] / (double)fa.lh[k]);
+    fa.s2x[k] = 1.0 / ((double)w / (double)rws[k]);
+    fa.s2y[k] = 1.0 / ((double)h / (double)rhs[k]);
+    fa.lframe[k] = (int64_t)(OP_N_PAF + OP_N_HEAT) * fa.lh[k] * fa.lw[k];
+    low_off[k + 1] = low_off[k] + (size_t)n * fa.lframe[k];
+  }
+  const char* fenv = getenv("OP_CUBIC_FUSED");
+  const bool fused = fenv && atoi(fenv) == 1 && cubic_fused_lds(fa) > 0;
+  RC(grow_buffer(c, (void**)&c->d_pmid, &c->pmid_bytes, (fused ? low_off[ns] : mid_off[ns]) * 4, "precise_mid"));
+  RC(grow_buffer(c, (void**)&c->d_psum, &c->psum_bytes, (size_t)n * fplanes * 4, "precise_sum"));
+  const size_t fbytes = (size_t)h * w * 3;
+  auto run_scale = [&](int k) -> int {
+    const int rw = rws[k], rh = rhs[k], pw = pws[k], ph = phs[k];
+    RC(ensure_geometry(c, n, ph, pw));
+    const Act& x0 = c->buf[B_X0];
+    RC(profiled(c, kProfInput, 0.0, 0.0, [&] {
+      return launch_preprocess_cubic(c->d_frames, (int64_t)w * 3, h, w, rh, rw, ph, pw, c->split, x0.p, n,
+                                     (int64_t)fbytes, (int64_t)x0.frame_floats(), c->stream);
+    }));
+    RC(run_forward(c));
+    // last-stage maps (lh, lw, cs) with the PAF / heat channels at paf_off / heat_off
+    const int lh = ph / 8, lw = pw / 8;
+    const float* mbase;
+    int64_t mrow, mframe;
+    int mpx, paf_off, heat_off;
+    if (c->split) {
+      const Act& m = c->buf[B_MAP32];
+      mbase = m.p;
+      mrow = (int64_t)lw * m.cs;
+      mframe = (int64_t)m.frame_floats();
+      mpx = m.cs;
+      paf_off = 0;
+      heat_off = 40;
+    } else {
+      const Act& cat = c->buf[B_CAT];
+      mrow = (int64_t)(lw + 2 * cat.pad) * cat.cs;
+      mframe = (int64_t)cat.frame_floats();
+      mbase = cat.p + cat.pad * mrow + (int64_t)cat.pad * cat.cs;
+      mpx = cat.cs;
+      paf_off = kCatPaf;
+      heat_off = kCatHeat;
+    }
+    if (fused) {
+      float* low = c->d_pmid + low_off[k];
+      fa.low[k] = low;
+      RC(profiled(c, kProfMapResize, 0.0, 0.0, [&] {
+        RC(launch_maps_planar(mbase + paf_off, mrow, mpx, mframe, lh, lw, OP_N_PAF, low, 0, OP_N_PAF + OP_N_HEAT, n,
+                              c->stream));
+        return launch_maps_planar(mbase + heat_off, mrow, mpx, mframe, lh, lw, OP_N_HEAT, low, OP_N_PAF,
+                                  OP_N_PAF + OP_N_HEAT, n, c->stream);
+      }));
+    } else {
+      // :461 / :465 cubic to the padded size (the heat by fx = fy = downscale: the same mapping),
+      // stored planar (cn, ph, pw) so the second resize reads coalesced rows; kept for every scale
+      // and frame until the fused second pass below; every frame of the scale in one launch per map
+      const int64_t pp = (int64_t)ph * pw;
+      const int64_t mid_f = pp * (OP_N_PAF + OP_N_HEAT);
+      float* mid_paf = c->d_pmid + mid_off[k];
+      float* mid_heat = mid_paf + (size_t)pp * OP_N_PAF;
+      RC(profiled(c, kProfMapResize, 0.0, 0.0, [&] {
+        RC(launch_resize_cubic_f32_frames(mbase + paf_off, mrow, mpx, mframe, lh, lw, OP_N_PAF, mid_paf, mid_f, ph, pw,
+                                          n, c->stream));
+        return launch_resize_cubic_f32_frames(mbase + heat_off, mrow, mpx, mframe, lh, lw, OP_N_HEAT, mid_heat, mid_f, ph,
+                                              pw, n, c->stream);
+      }));
+    }
+    return OP_OK;
+  };
+  // Round 6: the scales whose padded input is at most a quarter of the
+  // largest's (1280x720: scales 0.5 and 1.0) run on a second stream, enqueued first, so their
+  // launches -- a fraction of a round of workgroups each -- fill the rounds the large scales'
+  // launches leave partly idle.  Each scale has its own activation arena (ensure_geometry caches one
+  // per geometry, up to 6), its own region of d_pmid and, per stream, its own split-K workspace;
+  // the side stream starts after everything queued on the compute stream (the staged frames, the
+  // previous step's reads of d_pmid) and the compute stream waits for it before the scale mean.
+  // OP_PRECISE_STREAMS=1 (read per call) runs every scale on the compute stream; never under capture,
+  // nor while per-class profiling is on (op_profile: event pairs on two streams would overlap, and
+  // the per-class sums -- the 7x7 roofline's launch time -- would count the overlap twice).
+  const char* ps_env = getenv("OP_PRECISE_STREAMS");
+  hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
+  OP_HIP_CHECK(hipStreamIsCapturing(c->stream, &cap_st));
+  std::vector<int> side, mainv;
+  int64_t big = 0;
+  for (int k = 0; k < ns; ++k) big = std::max<int64_t>(big, (int64_t)phs[k] * pws[k]);
+  for (int k = 0; k < ns; ++k) {
+    const bool small = ns > 1 && 4 * (int64_t)phs[k] * pws[k] <= big;
+    (small && !(ps_env && atoi(ps_env) == 1) && !c->prof && cap_st == hipStreamCaptureStatusNone ? side : mainv)
+        .push_back(k);
+  }
+  if (!side.empty()) {
+    if (!c->side_stream) {
+      OP_HIP_CHECK(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
+      OP_HIP_CHECK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+      OP_HIP_CHECK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+    }
+    OP_HIP_CHECK(hipEventRecord(c->ev_fork, c->stream));
+    OP_HIP_CHECK(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
+    c->main_stream = c->stream;
+    c->stream = c->side_stream;
+    int rc = OP_OK;
+    for (int k : side)
+      if ((rc = run_scale(k)) != OP_OK) break;
+    c->stream = c->main_stream;
+    c->main_stream = nullptr;
+    // the join is recorded and waited for even after a failure, so no later work on the compute
+    // stream can overtake what the side stream still has queued
+    OP_HIP_CHECK(hipEventRecord(c->ev_join, c->side_stream));
+    if (rc != OP_OK) {
+      OP_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
+      return rc;
+    }
+    census_add(OP_CENSUS_PRECISE_SIDE);
+  }
+  for (int k : mainv) {
+    const int rc = run_scale(k);
+    if (rc != OP_OK) {
+      if (!side.empty()) OP_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
+      return rc;
+    }
+  }
+  if (!side.empty()) OP_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
+  // :462-463 / :466-467 / :469-470 every scale's crop to rh x rw and cubic to h x w, summed in scale
+  // order and divided by the scale count: one pass per frame over the PAF and heat planes
+  census_add(fused ? OP_CENSUS_CUBIC_FUSED : OP_CENSUS_CUBIC_TWO_PASS);
+  if (fused) {
+    bool taken = false;
+    RC(profiled(c, kProfMapResize, 0.0, 0.0, [&] {
+      return launch_resize_cubic_fused_mean(fa, c->d_psum, n, h, w, OP_N_PAF, OP_N_HEAT, c->stream, &taken);
+    }));
+    if (!taken) {
+      set_error("detect_precise: fused map resize refused a checked shape");
+      return OP_ERR_STATE;
+    }
+  }
+  // round 4: every frame in one launch, a block of 8 output rows making each source row's
+  // horizontal sums once (resize_cubic_f32_planar_mean_rows); OP_CUBIC_ROWS=0 selects the per-frame
+  // form (A/B aid, read per call)
+  bool rows_done = false;
+  const char* renv = getenv("OP_CUBIC_ROWS");
+  if (!fused && !(renv && atoi(renv) == 0)) {
+    CubicMeanArgs a{};
+    a.ns = ns;
+    for (int k = 0; k < ns; ++k) {
+      const int64_t pp = (int64_t)phs[k] * pws[k];
+      a.src[k] = c->d_pmid + mid_off[k];
+      a.fstride[k] = pp * (OP_N_PAF + OP_N_HEAT);
+      a.cstride[k] = pp;
+      a.sstride[k] = pws[k];
+      a.sh[k] = rhs[k];
+      a.sw[k] = rws[k];
+      a.scx[k] = 1.0 / ((double)w / (double)rws[k]);  // cv_cubic_scale (cvcubic.hpp)
+      a.scy[k] = 1.0 / ((double)h / (double)rhs[k]);
+    }
+    const char* tenv = getenv("OP_CUBIC_TILE");
+    const bool tile = tenv && atoi(tenv) == 1;
+    RC(profiled(c, kProfMapResize, 0.0, 0.0, [&] {
+      if (tile)
+        RC(launch_resize_cubic_f32_planar_mean_tile(a, c->d_psum, fplanes, n, h, w, OP_N_PAF, OP_N_HEAT, c->stream,
+                                                    &rows_done));
+      if (rows_done) return OP_OK;
+      return launch_resize_cubic_f32_planar_mean_rows(a, c->d_psum, fplanes, n, h, w, OP_N_PAF, OP_N_HEAT, c->stream,
+                                                      &rows_done);
+    }));
+  }
+  if (rows_done) census_add(OP_CENSUS_CUBIC_ROWS);
+  for (int f = 0; f < n && !fused && !rows_done; ++f) {
+    CubicMeanArgs a{};
+    a.ns = ns;
+    for (int k = 0; k < ns; ++k) {
+      const int64_t pp = (int64_t)phs[k] * pws[k];
+      a.src[k] = c->d_pmid + mid_off[k] + (size_t)f * pp * (OP_N_PAF + OP_N_HEAT);
+      a.cstride[k] = pp;
+      a.sstride[k] = pws[k];
+      a.sh[k] = rhs[k];
+      a.sw[k] = rws[k];
+      a.scx[k] = 1.0 / ((double)w / (double)rws[k]);  // cv_cubic_scale (cvcubic.hpp): OpenCV's f64 inverse scale
+      a.scy[k] = 1.0 / ((double)h / (double)rhs[k]);
+    }
+    RC(profiled(c, kProfMapResize, 0.0, 0.0, [&] {
+      return launch_resize_cubic_f32_planar_mean(a, c->d_psum + f * fplanes, h, w, OP_N_PAF, OP_N_HEAT, c->stream);
+    }));
+  }
+  // :474-482 post-process at the original resolution: img_len = orig_w, no rescale.  With staged
+  // full-resolution maps (op_stage_maps at the frame size + op_use_staged_maps) the post-process
+  // reads those instead of the averaged maps (which are still computed).
+  const float* post_maps = c->d_psum;
+  if (c->use_maps && staged) {
+    if (c->fm_n < n || c->fm_h != h || c->fm_w != w) {
+      set_error("staged full-resolution maps do not match the staged frames (n, h, w)");
+      return OP_ERR_STATE;
+    }
+    post_maps = c->d_fmaps;
+  }
+  RC(ensure_post(c, n, h, w));
+  PostShape s;
+  post_shape(c, s, n, h, w, h, w, (double)w, 1.0, 1.0);
+  post_record(c, 2, nullptr, post_maps, fplanes, s);
+  const float* sum_heat0 = post_maps + (size_t)OP_N_PAF * h * w;
+  RC(profiled(c, kProfPost, 0.0, 0.0, [&] {
+    RC(launch_peaks_from_full(sum_heat0, OP_N_JOINTS, h, w, s, c->pb, c->stream, fplanes));
+    RC(launch_connections_full(post_maps, h, w, s, c->pb, c->stream, fplanes));
+    return launch_grouping(s, c->pb, c->stream);
+  }));
+  *net_w = pws[ns - 1];
+  *net_h = phs[ns - 1];
+  return OP_OK;
+}
+
+int op_detect_precise(op_ctx* c, const uint8_t* bgr, int32_t h, int32_t w, int64_t row_stride, double* poses,
+                      double* scores, int32_t cap, op_frame_result* res, float* pafs_out, float* heat_out) {
+  using namespace op;
+  RC(check_ctx(c, true));
+  if (!bgr || !res || h < 11 || w < 11 || row_stride < (int64_t)w * 3 || c->prm.n_scales < 1) {
+    set_error("op_detect_precise: bad arguments (frame >= 11 x 11, at least one inference scale)");
+    return OP_ERR_INVALID;
+  }
+  c->up_slot = -1;  // a pending op_upload_frames is replaced
+  RC(upload_one_frame(c, bgr, h, w, row_stride));
+  // the staged frame set is replaced by this frame (its result stays fetchable as frame 0)
+  c->st_n = 0;
+  int net_w = 0, net_h = 0;
+  RC(precise_run(c, 1, h, w, &net_w, &net_h, false));
+  c->st_n = 1;
+  c->st_h = h;
+  c->st_w = w;
+  c->st_precise = true;
+  c->st_net_w = net_w;
+  c->st_net_h = net_h;
+  const float* sum_paf = c->d_psum;
+  const float* sum_heat = c->d_psum + (size_t)OP_N_PAF * h * w;
+  if (pafs_out)
+    OP_HIP_CHECK(hipMemcpyAsync(pafs_out, sum_paf, (size_t)OP_N_PAF * h * w * 4, hipMemcpyDeviceToHost, c->stream));
+  if (heat_out)
+    OP_HIP_CHECK(hipMemcpyAsync(heat_out, sum_heat, (size_t)OP_N_HEAT * h * w * 4, hipMemcpyDeviceToHost, c->stream));
+  OP_HIP_CHECK(hipStreamSynchronize(c->stream));
+  RC(guard_check("op_detect_precise"));
+  memset(res, 0, sizeof(*res));
+  res->map_w = w;
+  res->map_h = h;
+  res->net_w = net_w;
+  res->net_h = net_h;
+  return read_result(c, 0, poses, scores, cap, res);
+}
+
+int op_run_staged_precise(op_ctx* c) {
+  using namespace op;
+  RC(check_ctx(c, true));
+  RC(take_upload(c));
+  if (c->st_n < 1 || c->st_h < 11 || c->st_w < 11 || c->prm.n_scales < 1) {
+    set_error("op_run_staged_precise: no staged frames (>= 11 x 11) or no inference scale");
+    return OP_ERR_STATE;
+  }
+  int net_w = 0, net_h = 0;
+  RC(precise_run(c, c->st_n, c->st_h, c->st_w, &net_w, &net_h, true));
+  c->st_precise = true;
+  c->st_net_w = net_w;
+  c->st_net_h = net_h;
+  return OP_OK;
+}
+
+int op_resize_cubic(op_ctx* c, const void* src, int32_t dtype, int32_t h, int32_t w, int32_t cn, void* dst,
+                    int32_t out_h, int32_t out_w) {
+  using namespace op;
+  RC(check_ctx(c, false));
+  if (!src || !dst || (dtype != 0 && dtype != 1) || h < 1 || w < 1 || cn < 1 || out_h < 1 || out_w < 1) {
+    set_error("op_resize_cubic: bad arguments");
+    return OP_ERR_INVALID;
+  }
+  const size_t es = dtype == 0 ? 1 : 4;
+  const size_t inb = (size_t)h * w * cn * es, outb = (size_t)out_h * out_w * cn * es;
+  RC(ensure_scratch(c, inb + 256 + outb));
+  char* din = (char*)c->d_scratch;
+  char* dout = din + (inb + 255) / 256 * 256;
+  OP_HIP_CHECK(hipMemcpyAsync(din, src, inb, hipMemcpyHostToDevice, c->stream));
+  if (dtype == 0)
+    RC(launch_resize_cubic_u8((const uint8_t*)din, (int64_t)w * cn, h, w, cn, (uint8_t*)dout, out_h, out_w, c->stream));
+  else
+    RC(launch_resize_cubic_f32((const float*)din, (int64_t)w * cn, cn, h, w, cn, (float*)dout, out_h, out_w, 0, 1.0f,
+                               c->stream));
+  OP_HIP_CHECK(hipMemcpyAsync(dst, dout, outb, hipMemcpyDeviceToHost, c->stream));
+  OP_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return OP_OK;
+}
+
+}  // extern "C"

@@ -43,7 +43,7 @@ def record_bytes(max_persons):
 
 
 def pack_records(results, max_persons):
-    """Host-side records, byte-identical to the device's pack_records (runtime.hip).
+    """Host-side records, byte-identical to the device's pack_records (gather.hip).
     results: [(frame_id, status, n_peaks, poses (P,18,3), scores (P,))] -> (n, record_bytes) uint8."""
     rb = record_bytes(max_persons)
     out = np.zeros((len(results), rb), np.uint8)

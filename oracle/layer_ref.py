@@ -151,7 +151,7 @@ def _gemm_ideal(run, name, xg, W, b, last):
 def _kernel_channel_order(xg, W):
     """The 185-channel stage input in the order the kernels walk it: a 192-channel pixel with the
     feature at 0..127, heat at 128..146 and paf at 152..189, zeros between (csrc/common.hpp kCatFeat /
-    kCatHeat / kCatPaf; runtime.hip cat_logical packs Mconv1's weights the same way).  The order is
+    kCatHeat / kCatPaf; weights.hip cat_logical packs Mconv1's weights the same way).  The order is
     part of the yardstick: measured on the GPU in fp32, Mconv1's error has the r.m.s. of the
     sequential sum in this order, 25 % above that of the (paf, heat, feature) order."""
     if xg.shape[2] != 185:

@@ -48,7 +48,7 @@ def apply(ctx, cfg, precision, monkeypatch):
 
 def conv11_mode(cfg):
     """Which conv1_1 the bf16x3 forward runs: conv1_pair.hip's split-product MFMA form under the conv_big
-    families (algo 4, 5), conv11.hip's f32 FMAs otherwise (runtime.hip run_forward)."""
+    families (algo 4, 5), conv11.hip's f32 FMAs otherwise (forward.hip run_forward)."""
     return "mfma" if cfg.get("algo", 4) in (4, 5) else "f32"
 
 

@@ -112,6 +112,20 @@ def test_library_resolves_its_own_symbols():
     assert not own, own
 
 
+def test_every_unit_is_linked():
+    """Every csrc/*.hip is an object of the Makefile's OBJS and every object of OBJS has a source: a
+    unit left out of OBJS still enters the source digest (it globs *.hip) and would surface only as
+    an unresolved symbol when the library loads."""
+    csrc = os.path.join(REPO, PKG_NAME, "csrc")
+    objs = re.search(r"^OBJS\s*=\s*(.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M).group(1).split()
+    assert len(objs) == len(set(objs)) and all(o.endswith(".o") for o in objs), objs
+    stems = {o[:-2] for o in objs}
+    hip = {f[:-4] for f in os.listdir(csrc) if f.endswith(".hip")}
+    assert hip <= stems, "not in OBJS: %s" % sorted(hip - stems)
+    for s in stems - hip:
+        assert os.path.isfile(os.path.join(csrc, s + ".cpp")), "OBJS names %s.o, which has no source" % s
+
+
 @pytest.mark.parametrize("preset", [None, "4", "16"])
 def test_loader_leaves_the_environment_alone(preset):
     """Loading the library does not rewrite the host process's environment (round 3: the
