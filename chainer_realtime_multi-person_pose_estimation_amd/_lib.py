@@ -36,6 +36,7 @@ EXPORTED = (
     "op_train_enable_layer", "op_train_set_grad_scale", "op_train_step",
     "op_make_labels", "op_train_step_poses", "op_train_last_label_ms",
     "op_train_eval", "op_train_eval_poses", "op_train_get_state", "op_train_set_state",
+    "op_train_buffer_info", "op_train_read_buffer",
 )
 ARCH = {"facenet": 1, "handnet": 2}
 MAX_SCALES = 8
@@ -163,6 +164,8 @@ def lib():
         "op_train_eval_poses": ([P, I32, P, P, P, P, D, D, P], ctypes.c_int),
         "op_train_get_state": ([P, P, P, P, P, P], ctypes.c_int),
         "op_train_set_state": ([P, P, P, P, P, P], ctypes.c_int),
+        "op_train_buffer_info": ([I32, ctypes.POINTER(ctypes.c_char_p), P, P], ctypes.c_int),
+        "op_train_read_buffer": ([P, I32, I32, P, I64], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -300,6 +303,22 @@ def probe_table():
     for i in range(N_PROBE_POINTS):
         check(lib().op_forward_probe_info(i, ctypes.byref(name), ctypes.byref(ch), ctypes.byref(div)),
               "op_forward_probe_info")
+        out.append((name.value.decode(), ch.value, div.value))
+    return out
+
+
+N_TRAIN_BUFFERS = 89
+
+
+def train_buffer_table():
+    """[(name, channels, divisor)] of the training step's activation buffers (op_train_buffer_info):
+    buffer i is (n, channels, h / divisor, w / divisor), physical channels."""
+    out = []
+    name = ctypes.c_char_p()
+    ch, div = ctypes.c_int32(), ctypes.c_int32()
+    for i in range(N_TRAIN_BUFFERS):
+        check(lib().op_train_buffer_info(i, ctypes.byref(name), ctypes.byref(ch), ctypes.byref(div)),
+              "op_train_buffer_info")
         out.append((name.value.decode(), ch.value, div.value))
     return out
 
@@ -979,6 +998,18 @@ class TrainContext(object):
         ps = [(ctypes.c_void_p * len(self.table))(*[a.ctypes.data for a in arrs[key]])
               for key in ("mW", "vW", "mb", "vb")]
         check(lib().op_train_set_state(self.h_, ps[0], ps[1], ps[2], ps[3], ptr(t)), "op_train_set_state")
+
+    def buffers(self):
+        """[(name, channels, divisor)] of the step's activation buffers (``train_buffer_table``)."""
+        return train_buffer_table()
+
+    def read(self, i, grad=False):
+        """Activation (or gradient) buffer i as the last step left it (op_train_read_buffer, a test
+        aid): (n, channels, h / divisor, w / divisor) f32."""
+        _, ch, div = self.buffers()[int(i)]
+        out = np.empty((self.n, ch, self.h // div, self.w // div), np.float32)
+        check(lib().op_train_read_buffer(self.h_, int(i), int(bool(grad)), ptr(out), out.size), "op_train_read_buffer")
+        return out
 
 
 def pack_poses(poses_per_frame, n=None):

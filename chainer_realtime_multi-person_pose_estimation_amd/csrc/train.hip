@@ -327,18 +327,23 @@ __global__ __launch_bounds__(256) void tr_breduce(const float* __restrict__ part
 }
 
 // Chainer AdamRule.update_core (eta 1, no weight decay): grad *= scale (GradientScaling hook);
-// m += (1 - b1)(g - m); v += (1 - b2)(g^2 - v); p -= lr * m / (sqrt(v) + eps)
+// m += (1 - b1)(g - m); v += (1 - b2)(g^2 - v); p -= lr * m / (sqrt(v) + eps).  The arithmetic is in
+// double (the kernel is bound by its seven f32 streams) and p, m, v are each rounded to f32 once: in
+// f32 the thirteen roundings on the way to p, and 1.0f - (float)0.999 being 1.3e-5 off 0.001, left p
+// and v further from the rule than one rounding each (test_adam_step_from_random_moments in
+// tests/test_gpu_train.py has the figures).  omb1, omb2: 1 - beta.
 __global__ __launch_bounds__(256) void tr_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                               float* __restrict__ v, int64_t n, float scale, float lr, float b1,
-                                               float b2, float eps) {
+                                               float* __restrict__ v, int64_t n, float scale, double lr, double omb1,
+                                               double omb2, double eps) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float gr = g[i] * scale;
-  const float mm = m[i] + (1.0f - b1) * (gr - m[i]);
-  const float vv = v[i] + (1.0f - b2) * (gr * gr - v[i]);
-  m[i] = mm;
-  v[i] = vv;
-  p[i] -= lr * mm / (sqrtf(vv) + eps);
+  const double gr = (double)(g[i] * scale);  // the hook's product is f32 (train_coco_pose_estimation.py:38)
+  const double m0 = m[i], v0 = v[i];
+  const double mm = m0 + omb1 * (gr - m0);
+  const double vv = v0 + omb2 * (gr * gr - v0);
+  m[i] = (float)mm;
+  v[i] = (float)vv;
+  p[i] = (float)((double)p[i] - lr * mm / (sqrt(vv) + eps));
 }
 
 // forward packing [c8][tap][cop][8] (input channel = physical p, cat map) and input-gradient packing
@@ -415,6 +420,7 @@ struct op_train_ctx {
   bool lab_timed = false;
   double alpha = 1e-4, beta1 = 0.9, beta2 = 0.999, eps = 1e-8;
   bool have_weights = false;
+  bool stepped = false;  // a step has completed: op_train_read_buffer has something to read
 };
 
 namespace op {
@@ -560,6 +566,32 @@ int tr_pack_layer(op_train_ctx* c, int l, const TConv& cv) {
   OP_AFTER_LAUNCH("tr_pack", c->stream);
   OP_HIP_CHECK(hipGetLastError());
   return OP_OK;
+}
+
+// op_train_buffer_info's table (host only): build_graph's buffers; a conv output carries its
+// layer's name
+struct TBufTable {
+  std::string name[T_NB];
+  TBuf def[T_NB];
+};
+const TBufTable& buffer_table() {
+  static const TBufTable table = [] {
+    TBufTable t;
+    op_train_ctx g;
+    g.L = train_layers();
+    build_graph(&g);
+    for (int i = 0; i < T_NB; ++i) t.def[i] = g.bdef[i];
+    t.name[T_X0] = "input";
+    t.name[T_P1] = "pool1";
+    t.name[T_P2] = "pool2";
+    t.name[T_P3] = "pool3";
+    for (int s = 0; s < 5; ++s) t.name[T_CAT0 + s] = "stage" + std::to_string(s + 2) + "_input";
+    t.name[T_OUT6] = "stage6_maps";
+    for (const auto& cv : g.convs)
+      if (t.name[cv.out].empty()) t.name[cv.out] = g.L[cv.layer].name;
+    return t;
+  }();
+  return table;
 }
 
 // the exact-f32 forward over the first n frames of the activation buffers (n <= c->n)
@@ -752,12 +784,13 @@ int tr_step_core(op_train_ctx* c, double* losses) {
     const TLayer& d = c->L[l];
     const int64_t t = ++c->t_step[l];
     const double fix1 = 1.0 - std::pow(c->beta1, (double)t), fix2 = 1.0 - std::pow(c->beta2, (double)t);
-    const float lr = (float)(c->alpha * std::sqrt(fix2) / fix1);
+    const double lr = c->alpha * std::sqrt(fix2) / fix1;
+    const double omb1 = 1.0 - c->beta1, omb2 = 1.0 - c->beta2;
     const int64_t nw = (int64_t)d.co * d.ci * d.k * d.k;
     hipLaunchKernelGGL(tr_adam, dim3(nb(nw)), dim3(256), 0, c->stream, c->W[l], c->gW[l], c->mW[l], c->vW[l], nw,
-                       c->scale[l], lr, (float)c->beta1, (float)c->beta2, (float)c->eps);
+                       c->scale[l], lr, omb1, omb2, c->eps);
     hipLaunchKernelGGL(tr_adam, dim3(nb(d.co)), dim3(256), 0, c->stream, c->b[l], c->gb[l], c->mb[l], c->vb[l],
-                       (int64_t)d.co, c->scale[l], lr, (float)c->beta1, (float)c->beta2, (float)c->eps);
+                       (int64_t)d.co, c->scale[l], lr, omb1, omb2, c->eps);
   }
   for (const auto& cv : c->convs)
     if (c->enabled[cv.layer]) TRC(tr_pack_layer(c, cv.layer, cv));
@@ -771,6 +804,7 @@ int tr_step_core(op_train_ctx* c, double* losses) {
       for (size_t i = 0; i < nblocks; ++i) s += part[k * nblocks + i];
       losses[k] = s / (double)((int64_t)n * m.C * h8 * w8);
     }
+  c->stepped = true;
   return OP_OK;
 }
 
@@ -1165,6 +1199,48 @@ int op_train_set_state(op_train_ctx* c, const float* const* mW, const float* con
     c->t_step[l] = t[l];
   }
   return OP_OK;
+}
+
+static_assert(T_NB == OP_TRAIN_BUFFERS, "openpose_hip.h: OP_TRAIN_BUFFERS");
+
+int op_train_buffer_info(int32_t i, const char** name, int32_t* channels, int32_t* divisor) {
+  if (i < 0 || i >= T_NB || !name || !channels || !divisor) return OP_ERR_INVALID;
+  const TBufTable& t = buffer_table();
+  *name = t.name[i].c_str();
+  *channels = t.def[i].cs;
+  *divisor = t.def[i].div;
+  return OP_OK;
+}
+
+int op_train_read_buffer(op_train_ctx* c, int32_t i, int32_t grad, float* out, int64_t out_floats) {
+  TRC(tr_check(c));
+  if (!c->stepped) {
+    set_error("op_train_read_buffer: no completed step");
+    return OP_ERR_STATE;
+  }
+  if (i < 0 || i >= T_NB || !out) {
+    set_error("op_train_read_buffer: bad buffer index or null pointer");
+    return OP_ERR_INVALID;
+  }
+  const TView& v = grad ? c->grad[i] : c->act[i];
+  const int64_t want = (int64_t)c->n * v.cs * v.h * v.w;
+  if (out_floats != want) {
+    set_error("op_train_read_buffer: out_floats must be n * channels * (h / divisor) * (w / divisor) = " +
+              std::to_string(want));
+    return OP_ERR_INVALID;
+  }
+  // a dense staging tensor of its own, freed again: no buffer of the step is written
+  float* d = nullptr;
+  OP_HIP_CHECK(hipMalloc(&d, (size_t)want * 4));
+  const ActView a{0, v.pad, v.cs, v.h, v.w};
+  int rc = launch_extract_act(v.p, a, c->n, 0, c->n, 0, v.cs, d, 0, v.cs, c->stream);
+  if (rc == OP_OK && hipMemcpyAsync(out, d, (size_t)want * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
+    set_error("op_train_read_buffer: copy to the host failed");
+    rc = OP_ERR_HIP;
+  }
+  (void)hipStreamSynchronize(c->stream);
+  (void)hipFree(d);
+  return rc;
 }
 
 }  // extern "C"

@@ -525,6 +525,22 @@ int op_train_get_state(op_train_ctx* ctx, float* const* mW, float* const* vW, fl
 int op_train_set_state(op_train_ctx* ctx, const float* const* mW, const float* const* vW, const float* const* mb,
                        const float* const* vb, const int64_t* t /* 92 */);
 
+/* ---- Read-back of the step's tensors (a test aid, as op_forward_probe is for the forward) ----
+ * op_train_buffer_info (host only): buffer i of the step's OP_TRAIN_BUFFERS activation tensors in
+ * the order the step keeps them (the network input, every conv and pool output, the five 192-channel
+ * stage inputs in the inference layout: feature 0..127, heat 128..146, paf 152..189, and the stage-6
+ * maps: paf 0..37, heat 40..58), its physical channel count and size divisor.
+ * op_train_read_buffer copies the dense (n, channels, h / divisor, w / divisor) f32 interior of
+ * activation (grad == 0) or gradient (grad != 0) buffer i as the last completed op_train_step /
+ * op_train_step_poses left it: the gradient of a conv output is the one its weight- and
+ * input-gradient launches read (after the ReLU mask), that of a stage input or pool output the sum
+ * its consumers and the loss wrote.  Nothing of the training state is touched: a step, reads, a step
+ * equal two steps bit for bit.  OP_ERR_STATE before the first step; OP_ERR_INVALID for a bad index,
+ * out_floats != n * channels * (h / divisor) * (w / divisor) or a null pointer. */
+#define OP_TRAIN_BUFFERS 89
+int op_train_buffer_info(int32_t i, const char** name, int32_t* channels, int32_t* divisor);
+int op_train_read_buffer(op_train_ctx* ctx, int32_t i, int32_t grad, float* out, int64_t out_floats);
+
 #ifdef __cplusplus
 }
 #endif

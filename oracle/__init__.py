@@ -15,6 +15,10 @@ used as the *checker* for the MI355X path.  Only ``tests/``, ``__graft_entry__.s
   pixels, with the 3xBF16 product terms the kernels form, and the sequential-f32 accumulation
   yardstick; the reference of tests/test_gpu_layerwise.py (our own code, checked by
   tests/test_layer_ref.py).
+* ``oracle/train_ref.py``: float64 evaluation of one launch of the training backward (input, weight
+  and bias gradients, pool routing, loss gradient) from the tensors the device holds after a step,
+  with the sequential-f32 yardsticks; the reference of tests/test_gpu_train_layerwise.py (our own
+  code, pinned to float64 autograd by tests/test_train_ref.py).
 * ``oracle/cvresize.py``: OpenCV INTER_LINEAR restatement.  OpenCV is absent: parity unpinned.
 """
 from . import cvresize, forward, postproc  # noqa: F401

@@ -79,6 +79,29 @@ def test_probe_table_follows_the_layer_table(lib):
     assert len({t[0] for t in table}) == len(table)
 
 
+def test_train_buffer_table_follows_the_layer_table(lib):
+    """op_train_buffer_info (host only): OP_TRAIN_BUFFERS buffers; every layer but the map writers and
+    conv4_4_CPM (which write into the stage inputs / stage-6 maps) names the buffer it writes, with its
+    output channels; the stage inputs have the 192 physical channels of the inference layout."""
+    src = open(os.path.join(REPO, "include", "openpose_hip.h")).read()
+    table = lib.train_buffer_table()
+    assert len(table) == lib.N_TRAIN_BUFFERS == int(re.search(r"#define\s+OP_TRAIN_BUFFERS\s+(\d+)", src).group(1))
+    assert table[0] == ("input", 8, 1) and table[-1] == ("stage6_maps", 64, 8)
+    by_name = {t[0]: t for t in table}
+    assert len(by_name) == len(table)
+    into_maps = 0
+    for name, _, co, _ in lib.layer_table():
+        if name in by_name:
+            assert by_name[name][1] == co, name
+        else:
+            into_maps += 1
+    assert into_maps == 13 and [by_name["stage%d_input" % s] for s in range(2, 7)] == [("stage%d_input" % s, 192, 8) for s in range(2, 7)]
+    assert [by_name["pool%d" % i][2] for i in (1, 2, 3)] == [2, 4, 8]
+    name, ch, div = ctypes.c_char_p(), ctypes.c_int32(), ctypes.c_int32()
+    for i in (-1, len(table)):
+        assert lib.lib().op_train_buffer_info(i, ctypes.byref(name), ctypes.byref(ch), ctypes.byref(div)) == lib.OP_ERR_INVALID
+
+
 def test_forward_flops(lib):
     # SURVEY §6 / Appendix A: 271.9 GFLOP per 368x368 frame, 484.6 at 656x368
     assert abs(lib.forward_flops(368, 368) / 1e9 - 271.868) < 0.01
