@@ -37,6 +37,7 @@ EXPORTED = (
     "op_make_labels", "op_train_step_poses", "op_train_last_label_ms",
     "op_train_eval", "op_train_eval_poses", "op_train_get_state", "op_train_set_state",
     "op_train_buffer_info", "op_train_read_buffer",
+    "op_augment", "op_augment_last_ms", "op_augment_last_paths", "op_augment_tables",
 )
 ARCH = {"facenet": 1, "handnet": 2}
 MAX_SCALES = 8
@@ -166,6 +167,10 @@ def lib():
         "op_train_set_state": ([P, P, P, P, P, P], ctypes.c_int),
         "op_train_buffer_info": ([I32, ctypes.POINTER(ctypes.c_char_p), P, P], ctypes.c_int),
         "op_train_read_buffer": ([P, I32, I32, P, I64], ctypes.c_int),
+        "op_augment": ([I32, I32, P, P, P, P, I32, P, P], ctypes.c_int),
+        "op_augment_last_ms": ([I32, P], ctypes.c_int),
+        "op_augment_last_paths": ([I32, P], ctypes.c_int),
+        "op_augment_tables": ([P, P, P, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -11,7 +11,8 @@ float64 NumPy on the host: the path for a machine without the device, and the ch
 its ``coco_joint_indices`` (entity.py:106-124); ``parse_coco_annotation`` / ``valid_annotations``
 turn the person annotations of a COCO keypoints JSON (plain dicts, no pycocotools) into the
 integer-valued (people, 18, 3) pose arrays the labels are made from.  Image-side augmentation (the
-cv2 warps and colour distortion of coco_data_loader.py:60-205) is not part of this module.
+cv2 warps and colour distortion of coco_data_loader.py:60-205) is augment.py: ``augment_batch``
+turns annotated frames of any size into the images, poses and mask these labels are made from.
 """
 import numpy as np
 

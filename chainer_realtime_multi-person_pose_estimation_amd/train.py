@@ -18,6 +18,11 @@ network: ``synthetic_batch`` stands in with seeded images and COCO-like maps of 
 (people, 18, 3) poses as parse_coco_annotation makes them, and ``Updater.update_poses`` has the
 device generate the targets from them inside the step (labels.py, op_train_step_poses).
 
+``--data samples`` starts one stage earlier, where the reference's loader does: annotated frames of
+any size.  ``Updater.update_samples`` draws each sample's augmentation plan on the host (augment.py
+``draw_plan``: random resize, rotate, crop, colour, flip, in the reference's draw order), has the
+device produce the network-input frames and masks (op_augment) and hands them to ``update_poses``.
+
 ``Validator`` is the reference's (:129-159): every ``--val-interval`` iterations a fixed held-out set
 is scored with ``Updater.evaluate`` (op_train_eval: forward + compute_loss only, the training state
 is left alone) and ``val/loss``, ``val/paf``, ``val/heat`` join that log entry; at the same points
@@ -30,12 +35,14 @@ counts, iteration, alpha, frozen layers: extensions.snapshot(), :255) beside ``m
 import argparse
 import json
 import os
+import random
 import sys
 import time
 
 import numpy as np
 
 from . import _lib
+from . import augment as _augment
 from . import weights as _weights
 from .constants import params
 from .labels import train_params
@@ -92,6 +99,7 @@ class Updater(object):
                  resume=False, ctx=None):
         self.ctx = ctx if ctx is not None else _lib.TrainContext(n, h, w, device)
         self.n = int(n)
+        self.insize, self.device = (int(h), int(w)), int(device)
         self.names = [t[0] for t in self.ctx.table]
         self.enabled = {name: True for name in self.names}  # the device's flags, tracked for the snapshot
         self.iteration = 0
@@ -138,6 +146,19 @@ class Updater(object):
         self._schedule()
         return self._log(self.ctx.step_poses(preprocess(imgs), poses_per_frame, mask,
                                              train_params["heatmap_sigma"], train_params["paf_sigma"]))
+
+    def update_samples(self, samples, py_random, np_random):
+        """``update`` from what the reference's loader reads: samples = n of (img (h, w, 3) u8 BGR,
+        mask (h, w) nonzero = ignored or None, poses (people, 18, 3)) of any sizes.  augment_data
+        (coco_data_loader.py:195-205) runs as a host-drawn plan per sample (``py_random`` a
+        random.Random, ``np_random`` a np.random.RandomState, consumed in the reference's order) and
+        one device call for the pixels, then ``update_poses``."""
+        if self.insize[0] != self.insize[1]:
+            raise ValueError("update_samples: the crop is square, the context is %d x %d" % self.insize)
+        if len(samples) != self.n:
+            raise ValueError("update_samples: %d samples, the context holds %d" % (len(samples), self.n))
+        imgs, poses, mask = _augment.augment_batch(samples, self.insize[0], py_random, np_random, self.device)
+        return self.update_poses(imgs, poses, mask)
 
     def _log(self, losses):
         self.iteration += 1
@@ -294,6 +315,24 @@ def synthetic_poses(rng, n, h, w, people=4):
     return out
 
 
+SAMPLE_SIZES = ((240, 320), (333, 500))
+
+
+def synthetic_samples(rng, n, people=4, sizes=SAMPLE_SIZES):
+    """Seeded stand-in for get_img_annotation + parse_coco_annotation: n of (img, mask, poses) at
+    mixed sizes, a random image, a sparse ignore mask and ``synthetic_poses`` at that size (every
+    person with at least one visible joint, as the loader's min_keypoints filter guarantees)."""
+    out = []
+    for f in range(n):
+        h, w = sizes[f % len(sizes)]
+        img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+        mask = rng.random((h, w)) < 0.0005
+        poses = synthetic_poses(rng, 1, h, w, people)[0]
+        poses[:, 0, 2] = np.maximum(poses[:, 0, 2], 1)
+        out.append((img, mask, poses))
+    return out
+
+
 def validation_batches(seed, samples, valbatchsize, insize, data="maps", people=4):
     """The held-out set of the CLI: ``samples`` synthetic frames in batches of ``valbatchsize`` (the
     last one shorter), drawn once from a stream seeded apart from the training stream's."""
@@ -333,9 +372,10 @@ def main(argv=None, ctx=None):
     ap.add_argument("--resume", action="store_true", help="do not freeze the VGG layers")
     ap.add_argument("--out", "-o", default="result/test")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--data", choices=["maps", "poses"], default="maps",
-                    help="maps: host-made synthetic target maps; poses: synthetic keypoints, targets made on the device")
-    ap.add_argument("--people", type=int, default=4, help="people per frame (--data poses)")
+    ap.add_argument("--data", choices=["maps", "poses", "samples"], default="maps",
+                    help="maps: host-made synthetic target maps; poses: synthetic keypoints, targets made on the "
+                    "device; samples: synthetic annotated frames of mixed sizes, augmented on the device first")
+    ap.add_argument("--people", type=int, default=4, help="people per frame (--data poses, samples)")
     ap.add_argument("--resume-from", metavar="FILE", help="continue from a snapshot_iter_N.npz (the reference's "
                     "--resume FILE): weights, Adam state, iteration, alpha and frozen layers")
     ap.add_argument("--valbatchsize", "-b", type=int, default=4, help="validation minibatch size (<= --batchsize)")
@@ -361,9 +401,11 @@ def main(argv=None, ctx=None):
         if args.valbatchsize > args.batchsize:
             ap.error("--valbatchsize must not exceed --batchsize (validation runs in the training context)")
         validator = Validator(up, validation_batches(args.seed, args.val_samples, args.valbatchsize, args.insize,
-                                                     args.data, args.people), poses=args.data == "poses")
+                                                     "maps" if args.data == "maps" else "poses", args.people),
+                              poses=args.data != "maps")
     # (a resumed run draws fresh synthetic batches instead of replaying the stream from its start)
     rng = np.random.default_rng([args.seed, 2, up.iteration] if args.resume_from else args.seed)
+    py_random, np_random = random.Random(args.seed), np.random.RandomState(args.seed)  # the augmentation's draws
     os.makedirs(args.out, exist_ok=True)
     log, pending, saved = [], [], None
     for it in range(args.iteration):
@@ -377,6 +419,14 @@ def main(argv=None, ctx=None):
             label_ms = up.ctx.last_label_ms()  # device events around the label uploads + kernel
             extra = {"label_ms": label_ms, "step_ms": dt * 1e3 - label_ms}
             note = ", labels %.3f ms, step %.1f ms" % (label_ms, dt * 1e3 - label_ms)
+        elif args.data == "samples":
+            samples = synthetic_samples(rng, args.batchsize, args.people)
+            t0 = time.perf_counter()
+            loss, pl, hl = up.update_samples(samples, py_random, np_random)
+            dt = time.perf_counter() - t0
+            augment_ms, label_ms = _augment.last_ms(up.device), up.ctx.last_label_ms()
+            extra = {"augment_ms": augment_ms, "label_ms": label_ms}
+            note = ", augment %.3f ms, labels %.3f ms" % (augment_ms, label_ms)
         else:
             batch = synthetic_batch(rng, args.batchsize, args.insize, args.insize)
             t0 = time.perf_counter()

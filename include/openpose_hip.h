@@ -541,6 +541,50 @@ int op_train_set_state(op_train_ctx* ctx, const float* const* mW, const float* c
 int op_train_buffer_info(int32_t i, const char** name, int32_t* channels, int32_t* divisor);
 int op_train_read_buffer(op_train_ctx* ctx, int32_t i, int32_t grad, float* out, int64_t out_floats);
 
+/* ---- Training-sample augmentation (coco_data_loader.py:60-205: resize, rotate, crop, colour, flip) ----
+ * One sample's plan, every random draw already made on the host (augment.py draw_plan): the source
+ * is resized to rw x rh (cv2.resize, linear), warped by the 2x3 forward matrix R into a bw x bh
+ * image (cv2.warpAffine: cubic, border 128, for the image; linear on mask * 255, border 0, > 0 for
+ * the mask), of which rows y1 .. y2, columns x1 .. x2 are copied to rows y_from .. y_to, columns
+ * x_from .. x_to of an insize x insize crop filled with 127 / false (x2 < x1 or y2 < y1: nothing is
+ * copied); then, when colour != 0, BGR2HSV, clip(channel + (dh, ds, dv), 0, 255), HSV2BGR; then,
+ * when flip != 0, the horizontal flip.  degree and (ox, oy) are carried for the record only. */
+typedef struct op_augment_plan {
+  int32_t h, w;   /* source size */
+  int32_t rw, rh; /* resized size */
+  double degree;
+  double R[6]; /* row-major 2x3, after the bounding-box shift */
+  int32_t bw, bh; /* rotated size */
+  int32_t ox, oy; /* crop offset */
+  int32_t x1, y1, x2, y2, x_from, y_from, x_to, y_to;
+  int32_t colour, dh, ds, dv; /* colour != 0: the signed deltas apply */
+  int32_t flip;
+  int32_t insize;
+} op_augment_plan;
+/* A batch of n samples on `device`: bgr[f] is sample f's h x w x 3 u8 image with row_stride[f] bytes
+ * per row, mask[f] its h x w u8 ignore mask (nonzero = ignored; the array or an entry may be null:
+ * nothing ignored); outputs are host pointers.  Two kernels for the whole batch (the resize, then
+ * one fused pass per output pixel: the rotated image is never written), bit-identical to
+ * augment.py's augment_np.  Arguments are validated before any device call (OP_ERR_INVALID, the
+ * message names the field): null arrays, n < 1, insize < 1, sizes < 1, rw / rh / bw / bh above 16384
+ * (the warp keeps source coordinates as shorts), a plan's insize other than the call's, non-finite
+ * R, a copy window that does not fit insize or bw x bh, colour deltas outside [-10, 10], [-40, 40],
+ * [-30, 30]. */
+int op_augment(int32_t device, int32_t n, const uint8_t* const* bgr, const int64_t* row_stride,
+               const uint8_t* const* mask /* entries or the array may be null */, const op_augment_plan* plans,
+               int32_t insize, uint8_t* out_bgr /* n,insize,insize,3 */, uint8_t* out_mask /* n,insize,insize */);
+/* Device time (ms, stream events) of the uploads and kernels of the last op_augment that completed
+ * on `device`; OP_ERR_STATE before the first. */
+int op_augment_last_ms(int32_t device, double* ms);
+/* counts[2] of that call: output pixels whose warp taps were read from the tile's box staged in
+ * LDS, and from global memory (a tile whose source box exceeds the LDS budget); pixels outside
+ * their copy window count in neither.  OP_ERR_STATE before the first call. */
+int op_augment_last_paths(int32_t device, int64_t* counts);
+/* (host only) The tables the kernels read: warpAffine's remap weights, cubic [1024][16] and linear
+ * [1024][4] int16 (set ay * 32 + ax, rows of columns, every set sums to 1 << 15), and BGR2HSV's
+ * sdiv[256], hdiv[256] int32.  Any pointer may be null. */
+int op_augment_tables(int16_t* cubic, int16_t* linear, int32_t* sdiv, int32_t* hdiv);
+
 #ifdef __cplusplus
 }
 #endif
