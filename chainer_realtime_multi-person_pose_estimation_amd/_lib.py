@@ -38,6 +38,7 @@ EXPORTED = (
     "op_train_eval", "op_train_eval_poses", "op_train_get_state", "op_train_set_state",
     "op_train_buffer_info", "op_train_read_buffer",
     "op_augment", "op_augment_last_ms", "op_augment_last_paths", "op_augment_tables",
+    "op_ignore_masks", "op_ignore_masks_last_ms",
 )
 ARCH = {"facenet": 1, "handnet": 2}
 MAX_SCALES = 8
@@ -171,6 +172,8 @@ def lib():
         "op_augment_last_ms": ([I32, P], ctypes.c_int),
         "op_augment_last_paths": ([I32, P], ctypes.c_int),
         "op_augment_tables": ([P, P, P, P], ctypes.c_int),
+        "op_ignore_masks": ([I32, I32, P, P, P, P, P, P, P, P, P, P, P], ctypes.c_int),
+        "op_ignore_masks_last_ms": ([I32, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -1036,3 +1039,50 @@ def pack_mask(mask, n, h, w):
     if mk.shape != (n, h, w):
         raise ValueError("ignore mask: %s expected, got %s" % ((n, h, w), mk.shape))
     return mk
+
+
+def pack_annotations(images):
+    """images = n of (h, w, annotations as COCO.loadAnns returns them) -> the flat arrays of
+    op_ignore_masks (a dict keyed by its argument names).  The roles follow gen_masks
+    (gen_ignore_mask.py:28-36) with labels.train_params' thresholds; a segmentation outside the
+    declared limits raises ValueError naming the annotation (masks.segmentation_parts)."""
+    from . import masks as _masks
+    hw, ann_offsets, role, part_offsets, kind, data_offsets = [], [0], [], [0], [], [0]
+    xy, counts = [], []
+    for h, w, anns in images:
+        hw += [int(h), int(w)]
+        for ann in anns:
+            role.append(_masks.ann_role(ann))
+            for k, data in _masks.segmentation_parts(ann, int(h), int(w)):
+                kind.append(k)
+                data_offsets.append(data_offsets[-1] + len(data))
+                # one index space for both arrays: the other kind's slots are never read
+                xy.append(data if k == _masks.KIND_POLYGON else np.zeros(len(data)))
+                counts.append(data if k == _masks.KIND_RLE else np.zeros(len(data), np.uint32))
+            part_offsets.append(len(kind))
+        ann_offsets.append(len(role))
+    return dict(hw=np.array(hw, np.int32), ann_offsets=np.array(ann_offsets, np.int32), ann_role=np.array(role, np.int32),
+                part_offsets=np.array(part_offsets, np.int32), part_kind=np.array(kind, np.int32),
+                data_offsets=np.array(data_offsets, np.int64),
+                xy=np.ascontiguousarray(np.concatenate(xy), np.float64) if xy else np.zeros(0, np.float64),
+                counts=np.ascontiguousarray(np.concatenate(counts), np.uint32) if counts else np.zeros(0, np.uint32))
+
+
+def ignore_masks_call(device, n, packed, out_all=None, out_miss=None, out_ann=None):
+    """op_ignore_masks on ``pack_annotations``' arrays; out_* are lists of C-contiguous (h, w) u8
+    arrays (or None entries, or None) that the call fills."""
+    def table(arrays):
+        if arrays is None:
+            return None
+        for a in arrays:
+            if a is not None and not (a.dtype == np.uint8 and a.flags.c_contiguous):
+                raise ValueError("op_ignore_masks: outputs are C-contiguous uint8 arrays")
+        return (ctypes.c_void_p * max(len(arrays), 1))(*[a.ctypes.data if a is not None else None for a in arrays])
+
+    def arr(name):
+        return ptr(packed[name]) if packed[name].size else None
+
+    tabs = [table(out_all), table(out_miss), table(out_ann)]
+    check(lib().op_ignore_masks(int(device), int(n), ptr(packed["hw"]), ptr(packed["ann_offsets"]), arr("ann_role"),
+                                ptr(packed["part_offsets"]), arr("part_kind"), ptr(packed["data_offsets"]),
+                                arr("xy"), arr("counts"), *tabs), "op_ignore_masks")

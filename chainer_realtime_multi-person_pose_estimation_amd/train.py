@@ -22,6 +22,8 @@ device generate the targets from them inside the step (labels.py, op_train_step_
 any size.  ``Updater.update_samples`` draws each sample's augmentation plan on the host (augment.py
 ``draw_plan``: random resize, rotate, crop, colour, flip, in the reference's draw order), has the
 device produce the network-input frames and masks (op_augment) and hands them to ``update_poses``.
+``Updater.update_annotated`` starts at the raw COCO annotations: the device makes each image's ignore
+mask from the segmentations first (masks.py, op_ignore_masks: gen_ignore_mask.py's ``gen_masks``).
 
 ``Validator`` is the reference's (:129-159): every ``--val-interval`` iterations a fixed held-out set
 is scored with ``Updater.evaluate`` (op_train_eval: forward + compute_loss only, the training state
@@ -43,6 +45,8 @@ import numpy as np
 
 from . import _lib
 from . import augment as _augment
+from . import labels as _labels
+from . import masks as _masks
 from . import weights as _weights
 from .constants import params
 from .labels import train_params
@@ -159,6 +163,26 @@ class Updater(object):
             raise ValueError("update_samples: %d samples, the context holds %d" % (len(samples), self.n))
         imgs, poses, mask = _augment.augment_batch(samples, self.insize[0], py_random, np_random, self.device)
         return self.update_poses(imgs, poses, mask)
+
+    def update_annotated(self, samples, py_random, np_random):
+        """``update_samples`` from raw COCO annotations: samples = n of (img (h, w, 3) u8 BGR, all the
+        image's annotations as ``COCO.loadAnns`` returns them).  The ignore masks of the batch are made
+        on the device (gen_ignore_mask.py's ``gen_masks``; its PNG round trip, ``* 255`` then
+        ``== 255``, is lossless), the people are the annotations ``get_img_annotation`` keeps
+        (coco_data_loader.py:284-288), parsed by ``parse_coco_annotation``.  A sample without a valid
+        person raises ValueError naming its index: the reference's loader draws another image there
+        (:351-353), and so does the caller."""
+        if len(samples) != self.n:
+            raise ValueError("update_annotated: %d samples, the context holds %d" % (len(samples), self.n))
+        people = []
+        for f, (_, annotations) in enumerate(samples):
+            valid = _labels.valid_annotations(annotations)
+            if valid is None:
+                raise ValueError("update_annotated: sample %d has no valid person annotation" % f)
+            people.append(_labels.parse_coco_annotation(valid))
+        made = _masks.ignore_masks([(img.shape[0], img.shape[1], annotations) for img, annotations in samples], self.device)
+        return self.update_samples([(img, miss, poses) for (img, _), (_, miss), poses in zip(samples, made, people)],
+                                   py_random, np_random)
 
     def _log(self, losses):
         self.iteration += 1

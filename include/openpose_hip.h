@@ -585,6 +585,42 @@ int op_augment_last_paths(int32_t device, int64_t* counts);
  * sdiv[256], hdiv[256] int32.  Any pointer may be null. */
 int op_augment_tables(int16_t* cubic, int16_t* linear, int32_t* sdiv, int32_t* hdiv);
 
+/* ---- Ignore masks from COCO segmentations (gen_ignore_mask.py:23-37 gen_masks, COCO.annToMask) ----
+ * A batch of n images on `device`.  Image f is hw[2f] x hw[2f + 1] (h, w) and owns the annotations
+ * ann_offsets[f] .. ann_offsets[f + 1] - 1, in gen_masks' order; annotation a has the role ann_role[a]
+ * (what gen_masks does with its mask, decided by the caller: OP_MASK_KEEP mask_all |= mask;
+ * OP_MASK_MISS both |= mask; OP_MASK_CROWD mask_miss |= mask & ~mask_all, then mask_all |= mask) and
+ * the parts part_offsets[a] .. part_offsets[a + 1] - 1, whose union is its mask (annToMask); it may
+ * have none.  Part p is one polygon (part_kind[p] = OP_MASK_POLYGON: x0, y0, x1, y1, ... as doubles,
+ * at least 3 points) or one uncompressed RLE (OP_MASK_RLE: run lengths of 0s and 1s alternating,
+ * column-major, 0s first); its elements are xy[data_offsets[p] .. data_offsets[p + 1] - 1] or
+ * counts[the same range]: the two arrays share one index space, the slots of the other kind are
+ * not read (xy may be null when there is no polygon, counts when there is no RLE).
+ * out_all[f] / out_miss[f]: host pointers to h * w u8 (row-major, 0 / 1), gen_masks' mask_all and
+ * mask_miss of image f; out_ann[a]: annotation a's own mask.  Each of the three arrays, and any
+ * entry, may be null: not wanted.  The result is masks.py's gen_masks_np / ann_to_mask_np bit for bit
+ * (the polygon rasteriser restates pycocotools' rleFrPoly; that parity is unpinned).
+ * Three kernels for the whole batch: polygon edges into toggle bits (one thread per point of the
+ * 5x upsampled outline), RLE running sums into toggle bits, and per block of columns the parity
+ * fill, the union and the three role rules.
+ * Arguments are validated before any device call (OP_ERR_INVALID, the message names the field):
+ * null arrays, n < 1, h or w outside 1 .. 16384, offsets that do not start at 0 or decrease, an
+ * unknown role or kind, a polygon of odd length or fewer than 3 points, a coordinate that is not
+ * finite or above 65536 in magnitude, an outline of more than 2^31 - 1 upsampled points in the batch,
+ * an RLE whose counts do not sum to h * w. */
+#define OP_MASK_KEEP 0
+#define OP_MASK_MISS 1
+#define OP_MASK_CROWD 2
+#define OP_MASK_POLYGON 0
+#define OP_MASK_RLE 1
+int op_ignore_masks(int32_t device, int32_t n, const int32_t* hw, const int32_t* ann_offsets, const int32_t* ann_role,
+                    const int32_t* part_offsets, const int32_t* part_kind, const int64_t* data_offsets,
+                    const double* xy, const uint32_t* counts, uint8_t* const* out_all, uint8_t* const* out_miss,
+                    uint8_t* const* out_ann);
+/* Device time (ms, stream events) of the uploads and kernels of the last op_ignore_masks that
+ * completed on `device`; OP_ERR_STATE before the first. */
+int op_ignore_masks_last_ms(int32_t device, double* ms);
+
 #ifdef __cplusplus
 }
 #endif
