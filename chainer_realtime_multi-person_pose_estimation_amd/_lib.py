@@ -32,6 +32,7 @@ EXPORTED = (
     "op_set_conv_algo", "op_set_stage_layout", "op_set_batch_invariant", "op_set_peak_mode", "op_profile_classes", "op_run_staged_precise",
     "op_cpm_layer_count", "op_cpm_layer_info", "op_cpm_create", "op_cpm_destroy", "op_cpm_set_weights",
     "op_cpm_forward", "op_cpm_peaks", "op_cpm_detect", "op_cpm_detect_batch", "op_cpm_set_batch_invariant",
+    "op_cpm_probe_info", "op_cpm_forward_probe",
     "op_train_create", "op_train_destroy", "op_train_set_weights", "op_train_get_weights", "op_train_set_hyper",
     "op_train_enable_layer", "op_train_set_grad_scale", "op_train_step",
     "op_make_labels", "op_train_step_poses", "op_train_last_label_ms",
@@ -41,6 +42,7 @@ EXPORTED = (
     "op_ignore_masks", "op_ignore_masks_last_ms",
 )
 ARCH = {"facenet": 1, "handnet": 2}
+CPM_PROBE_HI = 256  # OP_CPM_PROBE_HI
 MAX_SCALES = 8
 PRECISION = {"fp32": 0, "bf16x3": 1}
 PEAK_BRANCH = {"cpu": 0, "gpu": 1}  # OP_PEAKS_CPU_BRANCH / OP_PEAKS_GPU_BRANCH
@@ -133,6 +135,8 @@ def lib():
         "op_cpm_destroy": ([P], ctypes.c_int),
         "op_cpm_set_weights": ([P, P, P], ctypes.c_int),
         "op_cpm_forward": ([P, P, I32, I32, I32, P], ctypes.c_int),
+        "op_cpm_probe_info": ([I32, I32, ctypes.POINTER(ctypes.c_char_p), P, P], ctypes.c_int),
+        "op_cpm_forward_probe": ([P, P, I32, I32, I32, I32, I32, I32, P, I64], ctypes.c_int),
         "op_cpm_peaks": ([P, P, I32, I32, I32, ctypes.c_float, I32, P, P], ctypes.c_int),
         "op_cpm_detect": ([P, P, I32, I32, I64, ctypes.c_float, I32, P, P], ctypes.c_int),
         "op_cpm_detect_batch": ([P, I32, P, P, P, P, ctypes.c_float, P, P, P], ctypes.c_int),
@@ -723,6 +727,20 @@ def cpm_layer_table(arch):
     return out
 
 
+def cpm_probe_table(arch):
+    """[(name, channels, divisor)] of op_cpm_forward_probe's points 0 .. 45 for FaceNet / HandNet, from
+    the library: the point's tensor is (frames, channels, h / divisor, w / divisor)."""
+    a = ARCH[arch]
+    out = []
+    name = ctypes.c_char_p()
+    ch, div = ctypes.c_int32(), ctypes.c_int32()
+    for i in range(N_PROBE_POINTS):
+        check(lib().op_cpm_probe_info(a, i, ctypes.byref(name), ctypes.byref(ch), ctypes.byref(div)),
+              "op_cpm_probe_info")
+        out.append((name.value.decode(), ch.value, div.value))
+    return out
+
+
 def _row_strided_u8(img):
     """A uint8 H x W x 3 view whose pixels are packed within each row (rows may be strided, e.g. a
     crop view into a larger image: the device upload packs them); anything else is copied."""
@@ -807,6 +825,24 @@ class CpmContext(object):
         n, _, h, w = x.shape
         out = np.empty((n, self.n_maps, h // 8, w // 8), np.float32)
         check(lib().op_cpm_forward(self.h, ptr(x), n, h, w, ptr(out)), "op_cpm_forward")
+        return out
+
+    def forward_probe(self, x, point, frames=None, hi=False):
+        """What probe point `point` of the forward wrote (include/openpose_hip.h: op_cpm_forward_probe),
+        as dense f32 (frames, channels, h / divisor, w / divisor); frames = (first, count), default all.
+        hi: the hi halves of the stored split pairs alone (OP_CPM_PROBE_HI) instead of hi + lo."""
+        x = np.ascontiguousarray(x, np.float32)
+        n, c, h, w = x.shape
+        if c != 3:
+            raise ValueError("expected (n, 3, h, w)")
+        f0, nf = (0, n) if frames is None else (int(frames[0]), int(frames[1]))
+        name, ch, div = ctypes.c_char_p(), ctypes.c_int32(), ctypes.c_int32()
+        check(lib().op_cpm_probe_info(ARCH[self.arch], int(point), ctypes.byref(name), ctypes.byref(ch),
+                                      ctypes.byref(div)), "op_cpm_probe_info")
+        out = np.empty((max(nf, 0), ch.value, h // div.value, w // div.value), np.float32)
+        check(lib().op_cpm_forward_probe(self.h, ptr(x), n, h, w, int(point) + (CPM_PROBE_HI if hi else 0), f0, nf,
+                                         ptr(out), out.size),
+              "op_cpm_forward_probe")
         return out
 
     @staticmethod

@@ -190,7 +190,8 @@ int launch_preprocess_split(const uint8_t* frames, int64_t frame_bytes, int64_t 
 int launch_extract_maps32(const float* m, int32_t cs, int32_t heat_off, int32_t n, int32_t h, int32_t w, float* paf,
                           float* heat, hipStream_t st);
 // An activation tensor as op_forward_probe's extraction reads it (ctx.hpp Act): fmt 0 f32
-// [hp][wp][cs], 1 split [hp][wp][cs] (8 hi then 8 lo bf16 per 8 channels), 2 split chunk-planar
+// [hp][wp][cs], 1 split [hp][wp][cs] (8 hi then 8 lo bf16 per 8 channels), 2 split chunk-planar,
+// 3 as 1 but the hi halves alone
 struct ActView {
   int32_t fmt, pad, cs, h, w;
 };

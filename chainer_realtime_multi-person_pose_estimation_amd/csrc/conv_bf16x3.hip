@@ -460,7 +460,9 @@ int launch_extract_maps32(const float* m, int32_t cs, int32_t heat_off, int32_t 
 // op_forward_probe: channels [c0, c0 + nc) of frames [f0, f0 + nf) of an activation tensor -> dense
 // f32 planar dst[f - f0][dst_c0 + c - c0][y][x] (dst_ch channels per frame).  One thread per
 // (frame, 8-channel group, pixel): fmt 0 reads 8 floats of the f32 [hp][wp][cs] layout, fmt 1 / 2 the
-// group's hi and lo pieces of the split layout ([hp][wp][cs] / chunk-planar) and returns hi + lo.
+// group's hi and lo pieces of the split layout ([hp][wp][cs] / chunk-planar) and returns hi + lo;
+// fmt 3 is fmt 1 returning the hi halves alone (hi + lo does not say which pair was stored when it
+// lies halfway between two bf16 values).
 __global__ __launch_bounds__(256) void extract_act(const char* __restrict__ in, ActView a, int f0, int nf, int c0, int nc,
                                                    float* __restrict__ dst, int dst_c0, int dst_ch) {
   const int groups = (nc + 7) / 8;
@@ -492,8 +494,8 @@ __global__ __launch_bounds__(256) void extract_act(const char* __restrict__ in, 
     const u16x4 l0 = *(const u16x4*)(p + ps), l1 = *(const u16x4*)(p + ps + 8);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      v[e] = bf16_to_f(h0[e]) + bf16_to_f(l0[e]);
-      v[e + 4] = bf16_to_f(h1[e]) + bf16_to_f(l1[e]);
+      v[e] = a.fmt == 3 ? bf16_to_f(h0[e]) : bf16_to_f(h0[e]) + bf16_to_f(l0[e]);
+      v[e + 4] = a.fmt == 3 ? bf16_to_f(h1[e]) : bf16_to_f(h1[e]) + bf16_to_f(l1[e]);
     }
   }
   float* o = dst + (((int64_t)f * dst_ch + dst_c0 + 8 * g) * a.h + y) * a.w + x;
@@ -505,7 +507,7 @@ __global__ __launch_bounds__(256) void extract_act(const char* __restrict__ in, 
 int launch_extract_act(const float* in, const ActView& a, int32_t n, int32_t f0, int32_t nf, int32_t c0, int32_t nc,
                        float* dst, int32_t dst_c0, int32_t dst_ch, hipStream_t st) {
   // every 8-channel group read lies inside the pixel's cs channels, every frame inside the tensor
-  if (a.fmt < 0 || a.fmt > 2 || a.h < 1 || a.w < 1 || a.pad < 0 || a.cs % 8 || c0 % 8 || c0 < 0 || nc < 1 ||
+  if (a.fmt < 0 || a.fmt > 3 || a.h < 1 || a.w < 1 || a.pad < 0 || a.cs % 8 || c0 % 8 || c0 < 0 || nc < 1 ||
       c0 + (nc + 7) / 8 * 8 > a.cs || (a.fmt == 2 && a.cs % 16) || f0 < 0 || nf < 1 || f0 + nf > n || dst_c0 < 0 ||
       dst_c0 + nc > dst_ch) {
     set_error("extract_act: bad channel or frame range");

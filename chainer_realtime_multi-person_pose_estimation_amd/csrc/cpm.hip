@@ -329,7 +329,8 @@ int cconv_pool(op_cpm_ctx* c, const CAct& in, const CAct& full, const CAct& pool
 // 1x1 pair in -> a (ReLU) -> b -> out slice (+ dense f32 copy): fused head kernel when it fits
 int cpair(op_cpm_ctx* c, const CAct& in, const CAct& mid, const CAct& out, int cout_off, const SConv& a, const SConv& b,
           const CAct* out32) {
-  static const bool off = getenv("OP_HEAD_FUSED") && atoi(getenv("OP_HEAD_FUSED")) == 0;
+  const char* hf = getenv("OP_HEAD_FUSED");  // read per call, as run_forward does
+  const bool off = hf && atoi(hf) == 0;
   if (!off) {
     HeadShape s;
     s.n = c->gn;
@@ -372,36 +373,101 @@ int cpair(op_cpm_ctx* c, const CAct& in, const CAct& mid, const CAct& out, int c
     if (_r) return _r;   \
   } while (0)
 
-int cpm_run(op_cpm_ctx* c) {
+// ---- probe points (op_cpm_forward_probe): the launch boundaries of cpm_run in execution order ----
+// (name, channels returned, size divisor); map points return the heat slice of CAT as stored
+// (cat_cs - 128 channels, the padding included) followed by the 128 feature channels: the order of
+// the reference's concat
+constexpr int kCpmProbePoints = 46;
+struct CpmProbe {
+  std::string name;
+  int channels, div, buf, c0;
+};
+const std::vector<CpmProbe>* cpm_probe_table(int arch) {
+  auto make = [](int arch) {
+    const std::vector<CpmLayer>& T = *cpm_table(arch);
+    const int cat = (128 + n_maps_of(arch) + 15) / 16 * 16;
+    std::vector<CpmProbe> v = {{"input", 3, 1, X0, 0},
+                               {"conv1_2+pool", 64, 2, P1, 0},
+                               {"conv2_1", 128, 2, C21, 0},
+                               {"conv2_2+pool", 128, 4, P2, 0},
+                               {"conv3_1", 256, 4, C3A, 0},
+                               {"conv3_2", 256, 4, C3B, 0},
+                               {"conv3_3", 256, 4, C3A, 0},
+                               {"conv3_4+pool", 256, 8, P3, 0},
+                               {"conv4_1", 512, 8, C4A, 0},
+                               {"conv4_2", 512, 8, C4B, 0},
+                               {"conv4_3", 512, 8, C4A, 0},
+                               {"conv4_4", 512, 8, C4B, 0},
+                               {"conv5_1", 512, 8, C4A, 0},
+                               {"conv5_2", 512, 8, C4B, 0},
+                               {"conv5_3_CPM", 128, 8, CAT, kCpmFeat},
+                               {"stage1", cat, 8, CAT, kCpmHeat}};
+    for (int s = 2; s <= 6; ++s) {
+      for (int i = 0; i < 5; ++i) v.push_back({T[17 + 7 * (s - 2) + i].name, 128, 8, i % 2 ? BRB : BRA, 0});
+      v.push_back({"stage" + std::to_string(s), cat, 8, CAT, kCpmHeat});
+    }
+    return v;
+  };
+  static const std::vector<CpmProbe> face = make(OP_ARCH_FACENET), hand = make(OP_ARCH_HANDNET);
+  return arch == OP_ARCH_FACENET ? &face : (arch == OP_ARCH_HANDNET ? &hand : nullptr);
+}
+
+// Extract what probe point `point` wrote (frames [f0, f0 + nf)) as dense f32 NCHW into d_out.
+// hi: the hi halves alone (OP_CPM_PROBE_HI) instead of hi + lo.
+int cpm_probe_extract(op_cpm_ctx* c, int point, int f0, int nf, float* d_out, bool hi) {
+  const CpmProbe& p = (*cpm_probe_table(c->arch))[point];
+  const CAct& a = c->buf[p.buf];
+  const ActView v{hi ? 3 : 1, a.pad, a.cs, a.h, a.w};
+  if (p.buf == CAT && p.c0 == kCpmHeat) {  // the buffer the next stage's Mconv1 reads
+    const int nh = c->cat_cs - 128;
+    CRC(launch_extract_act(a.p, v, c->gn, f0, nf, kCpmHeat, nh, d_out, 0, p.channels, c->stream));
+    return launch_extract_act(a.p, v, c->gn, f0, nf, kCpmFeat, 128, d_out, nh, p.channels, c->stream);
+  }
+  return launch_extract_act(a.p, v, c->gn, f0, nf, p.c0, p.channels, d_out, 0, p.channels, c->stream);
+}
+
+// stop_point >= 0 (op_cpm_forward_probe only): return right after the launches of probe point
+// stop_point; the default never matches the point counter, so every other caller enqueues the whole
+// forward.
+int cpm_run(op_cpm_ctx* c, int stop_point = -1) {
   CAct* B = c->buf;
   const SConv* L = c->L;
-  CRC(launch_conv1_pair(nullptr, 0, 0, 0, 0, B[X0].p, c->gn, c->gh, c->gw, c->w11, L[0].b, L[1].ws, L[1].b, B[P1].p,
-                        B[P1].pad, c->stream));
-  CRC(cconv(c, B[P1], 0, B[C21], 0, L[2], 128, true));
-  CRC(cconv_pool(c, B[C21], B[C22], B[P2], L[3], 128));
-  CRC(cconv(c, B[P2], 0, B[C3A], 0, L[4], 256, true));
-  CRC(cconv(c, B[C3A], 0, B[C3B], 0, L[5], 256, true));
-  CRC(cconv(c, B[C3B], 0, B[C3A], 0, L[6], 256, true));
-  CRC(cconv_pool(c, B[C3A], B[C34], B[P3], L[7], 256));
-  CRC(cconv(c, B[P3], 0, B[C4A], 0, L[8], 512, true));
-  CRC(cconv(c, B[C4A], 0, B[C4B], 0, L[9], 512, true));
-  CRC(cconv(c, B[C4B], 0, B[C4A], 0, L[10], 512, true));
-  CRC(cconv(c, B[C4A], 0, B[C4B], 0, L[11], 512, true));
-  CRC(cconv(c, B[C4B], 0, B[C4A], 0, L[12], 512, true));
-  CRC(cconv(c, B[C4A], 0, B[C4B], 0, L[13], 512, true));
-  CRC(cconv(c, B[C4B], 0, B[CAT], kCpmFeat, L[14], 128, true));  // conv5_3_CPM: the feature map
-  CRC(cpair(c, B[CAT], B[S1], B[CAT], kCpmHeat, L[15], L[16], nullptr));  // stage 1
+  int point = 0;  // probe points passed so far (point 0 is the network input, already in X0)
+  if (stop_point == 0) return OP_OK;
+// the launches of probe point `point + 1`: stop behind them when it is the probed one
+#define CPM_POINT(x)                         \
+  do {                                       \
+    CRC(x);                                  \
+    if (++point == stop_point) return OP_OK; \
+  } while (0)
+  CPM_POINT(launch_conv1_pair(nullptr, 0, 0, 0, 0, B[X0].p, c->gn, c->gh, c->gw, c->w11, L[0].b, L[1].ws, L[1].b,
+                              B[P1].p, B[P1].pad, c->stream));
+  CPM_POINT(cconv(c, B[P1], 0, B[C21], 0, L[2], 128, true));
+  CPM_POINT(cconv_pool(c, B[C21], B[C22], B[P2], L[3], 128));
+  CPM_POINT(cconv(c, B[P2], 0, B[C3A], 0, L[4], 256, true));
+  CPM_POINT(cconv(c, B[C3A], 0, B[C3B], 0, L[5], 256, true));
+  CPM_POINT(cconv(c, B[C3B], 0, B[C3A], 0, L[6], 256, true));
+  CPM_POINT(cconv_pool(c, B[C3A], B[C34], B[P3], L[7], 256));
+  CPM_POINT(cconv(c, B[P3], 0, B[C4A], 0, L[8], 512, true));
+  CPM_POINT(cconv(c, B[C4A], 0, B[C4B], 0, L[9], 512, true));
+  CPM_POINT(cconv(c, B[C4B], 0, B[C4A], 0, L[10], 512, true));
+  CPM_POINT(cconv(c, B[C4A], 0, B[C4B], 0, L[11], 512, true));
+  CPM_POINT(cconv(c, B[C4B], 0, B[C4A], 0, L[12], 512, true));
+  CPM_POINT(cconv(c, B[C4A], 0, B[C4B], 0, L[13], 512, true));
+  CPM_POINT(cconv(c, B[C4B], 0, B[CAT], kCpmFeat, L[14], 128, true));  // conv5_3_CPM: the feature map
+  CPM_POINT(cpair(c, B[CAT], B[S1], B[CAT], kCpmHeat, L[15], L[16], nullptr));  // stage 1
   for (int s = 0; s < 5; ++s) {
     const SConv* M = L + 17 + 7 * s;
-    CRC(cconv(c, B[CAT], 0, B[BRA], 0, M[0], 128, true));
+    CPM_POINT(cconv(c, B[CAT], 0, B[BRA], 0, M[0], 128, true));
     const CAct* src = &B[BRA];
     const CAct* dst = &B[BRB];
     for (int i = 1; i <= 4; ++i) {
-      CRC(cconv(c, *src, 0, *dst, 0, M[i], 128, true));
+      CPM_POINT(cconv(c, *src, 0, *dst, 0, M[i], 128, true));
       std::swap(src, dst);
     }
-    CRC(cpair(c, *src, B[S1], B[CAT], kCpmHeat, M[5], M[6], s == 4 ? &B[MAP32] : nullptr));
+    CPM_POINT(cpair(c, *src, B[S1], B[CAT], kCpmHeat, M[5], M[6], s == 4 ? &B[MAP32] : nullptr));
   }
+#undef CPM_POINT
   return OP_OK;
 }
 
@@ -561,6 +627,61 @@ int op_cpm_forward(op_cpm_ctx* c, const float* x, int32_t n, int32_t h, int32_t 
                      c->buf[MAP32].cs, c->nm, n, lh * lw, dmaps);
   OP_AFTER_LAUNCH("cpm_planar", c->stream);
   OP_HIP_CHECK(hipMemcpyAsync(maps, dmaps, outb, hipMemcpyDeviceToHost, c->stream));
+  OP_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return OP_OK;
+}
+
+int op_cpm_probe_info(int32_t arch, int32_t point, const char** name, int32_t* channels, int32_t* divisor) {
+  const auto* t = cpm_probe_table(arch);
+  if (!t || point < 0 || point >= kCpmProbePoints || !name || !channels || !divisor) {
+    set_error("op_cpm_probe_info: bad arch, point or null pointer");
+    return OP_ERR_INVALID;
+  }
+  const CpmProbe& p = (*t)[point];
+  *name = p.name.c_str();
+  *channels = p.channels;
+  *divisor = p.div;
+  return OP_OK;
+}
+
+int op_cpm_forward_probe(op_cpm_ctx* c, const float* x, int32_t n, int32_t h, int32_t w, int32_t point, int32_t frame0,
+                         int32_t nframes, float* out, int64_t out_floats) {
+  CRC(cpm_check(c, true));
+  const bool hi_only = point >= OP_CPM_PROBE_HI && point < OP_CPM_PROBE_HI + kCpmProbePoints;
+  if (hi_only) point -= OP_CPM_PROBE_HI;
+  if (!x || !out) {
+    set_error("op_cpm_forward_probe: null pointer");
+    return OP_ERR_INVALID;
+  }
+  if (point < 0 || point >= kCpmProbePoints) {
+    set_error("op_cpm_forward_probe: point must be 0 .. 45 (+ OP_CPM_PROBE_HI)");
+    return OP_ERR_INVALID;
+  }
+  if (h % 8 || w % 8 || h < 16 || w < 16 || n < 1) {
+    set_error("network input must be >= 16 and a multiple of 8");
+    return OP_ERR_INVALID;
+  }
+  if (frame0 < 0 || nframes < 1 || frame0 > n - nframes) {
+    set_error("op_cpm_forward_probe: frames [frame0, frame0 + nframes) must lie in [0, n)");
+    return OP_ERR_INVALID;
+  }
+  const CpmProbe& pi = (*cpm_probe_table(c->arch))[point];
+  const int64_t want = (int64_t)nframes * pi.channels * (h / pi.div) * (w / pi.div);
+  if (out_floats != want) {
+    set_error("op_cpm_forward_probe: out_floats must be nframes * channels * (h / divisor) * (w / divisor) = " +
+              std::to_string(want));
+    return OP_ERR_INVALID;
+  }
+  CRC(cpm_geometry(c, n, h, w));
+  const size_t xin = (size_t)n * 3 * h * w * 4;
+  CRC(cpm_scratch(c, xin + 256 + (size_t)want * 4));
+  float* dx = (float*)c->scratch;
+  float* dout = (float*)((char*)c->scratch + (xin + 255) / 256 * 256);
+  OP_HIP_CHECK(hipMemcpyAsync(dx, x, xin, hipMemcpyHostToDevice, c->stream));
+  CRC(launch_nchw_to_split16(dx, c->buf[X0].p, n, h, w, c->stream));
+  CRC(cpm_run(c, point));
+  CRC(cpm_probe_extract(c, point, frame0, nframes, dout, hi_only));
+  OP_HIP_CHECK(hipMemcpyAsync(out, dout, (size_t)want * 4, hipMemcpyDeviceToHost, c->stream));
   OP_HIP_CHECK(hipStreamSynchronize(c->stream));
   return OP_OK;
 }

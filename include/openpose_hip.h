@@ -425,6 +425,29 @@ int op_cpm_set_weights(op_cpm_ctx* ctx, const float* const* W, const float* cons
 /* FaceNet.__call__ / HandNet.__call__ (models/FaceNet.py:78-161): x (n, 3, h, w) f32 NCHW
  * (h, w multiples of 8) -> last-stage maps (n, C, h/8, w/8) f32. */
 int op_cpm_forward(op_cpm_ctx* ctx, const float* x, int32_t n, int32_t h, int32_t w, float* maps);
+/* A test aid, as op_forward_probe is for CocoPoseNet: the forward run from x up to and including the
+ * launches of probe point `point`, and the tensor that point wrote returned as dense f32 (nframes,
+ * channels, h/divisor, w/divisor) for frames [frame0, frame0 + nframes); split-stored values come
+ * back as hi + lo.  The points are the launch boundaries of the forward in execution order; a pair
+ * or a conv + pool that runs as two launches is still one point:
+ *   0 the network input as stored; 1 conv1_1+conv1_2+pool; 2 conv2_1; 3 conv2_2+pool; 4-6 conv3_1 ..
+ *   conv3_3; 7 conv3_4+pool; 8-11 conv4_1 .. conv4_4; 12, 13 conv5_1, conv5_2; 14 conv5_3_CPM (the
+ *   128-channel feature map); 15 the stage-1 pair conv6_1_CPM+conv6_2_CPM; then for stage s = 2 .. 6
+ *   at 16 + 6 (s - 2) + i: i = 0 .. 4 Mconv1 .. Mconv5, i = 5 the pair Mconv6+Mconv7.
+ * The map points (15, 21, ..., 45) return the stage buffer the next Mconv1 reads in the order of
+ * the reference's concat: its heat slice as stored with the channel padding (80 channels for
+ * FaceNet, 32 for HandNet; those from C on are 0), then the 128 feature channels.  A bad point,
+ * frame range, out_floats (!= nframes * channels * (h/divisor) * (w/divisor)) or null pointer is
+ * OP_ERR_INVALID before anything is launched, missing weights OP_ERR_STATE.  op_cpm_forward
+ * enqueues the same launches as without this entry point.
+ * point + OP_CPM_PROBE_HI returns the hi halves alone: hi + lo does not say which pair a kernel
+ * stored when it lies exactly halfway between two bf16 values (hi rounded up and lo = -half a step,
+ * or down and +half), and the next layer's products w_hi x_hi + w_hi x_lo + w_lo x_hi depend on it.
+ * op_cpm_probe_info: a point's name, channel count and size divisor (46 points, 0 .. 45). */
+#define OP_CPM_PROBE_HI 256
+int op_cpm_probe_info(int32_t arch, int32_t point, const char** name, int32_t* channels, int32_t* divisor);
+int op_cpm_forward_probe(op_cpm_ctx* ctx, const float* x, int32_t n, int32_t h, int32_t w, int32_t point,
+                         int32_t frame0, int32_t nframes, float* out, int64_t out_floats);
 /* compute_peaks_from_heatmaps, CPU branch (face_detector.py:58-84, hand_detector.py:68-94): for each
  * of the first c-1 maps of heatmaps (c, h, w): gaussian_filter(sigma 2.5), global max m; found[i] =
  * m > thresh (f32); keypoints[i] = [coords[1], coords[0], m] of np.where(map == m) flattened

@@ -3,7 +3,11 @@
 Single-layer reference for the probe points of ``op_forward_probe`` (include/openpose_hip.h): the
 layer, or fused group of layers, between two probe points, evaluated in float64 at chosen output
 pixels from the input the GPU actually gave it.  Our own NumPy code; nothing here is a restatement
-of the reference project beyond the layer wiring of models/CocoPoseNet.py:132-262.
+of the reference project beyond the layer wiring of models/CocoPoseNet.py:132-262 and, for
+``net="facenet"`` / ``"handnet"`` (the points of ``op_cpm_forward_probe``), of models/FaceNet.py:78-161
+/ models/HandNet.py:78-161, written down here as a table of our own (``_cpm_point_spec``) over the
+layer names of ``op_cpm_layer_info``.  The CPM nets run in bf16x3 only, conv1_1 in its ``"mfma"`` form
+(csrc/cpm.hip cpm_run calls launch_conv1_pair).
 
 Two precisions, as ``op_set_precision``:
 
@@ -67,12 +71,55 @@ def recon(x):
     return hi + lo
 
 
-def point_spec(point):
+NETS = ("posenet", "facenet", "handnet")
+CPM_MAPS = {"facenet": 71, "handnet": 22}  # C: the heat maps of models/FaceNet.py / models/HandNet.py
+CPM_FEATURE_POINT = 14  # conv5_3_CPM, the 128-channel feature map (posenet: point 11)
+
+
+def cpm_heat_channels(net):
+    """Channels of the heat slice a CPM map point returns: the stage buffer's 128 + C channels are
+    padded to a multiple of 16 (csrc/cpm.hip cat_cs), 80 for facenet and 32 for handnet; those from C
+    on are zero."""
+    return (128 + CPM_MAPS[net] + 15) // 16 * 16 - 128
+
+
+def _cpm_point_spec(point, net):
+    """The launches of csrc/cpm.hip cpm_run between two probe points.  Mconv1 of stage s reads the
+    logical concat (heat C, feature 128) out of the probed map point [heat C | zero pad | feature 128]:
+    its channel selector is an index array instead of a (c0, c1) slice."""
+    C = CPM_MAPS[net]
+    one = {2: "conv2_1", 4: "conv3_1", 5: "conv3_2", 6: "conv3_3", 8: "conv4_1", 9: "conv4_2", 10: "conv4_3",
+           11: "conv4_4", 12: "conv5_1", 13: "conv5_2", 14: "conv5_3_CPM"}
+    pooled = {3: "conv2_2", 7: "conv3_4"}
+    if point == 1:
+        return 0, [([("conv1_1", 0, 3)], True), ([("conv1_2", 0, 64)], True)], True
+    if point in one:
+        return point - 1, [([(one[point], 0, None)], True)], False
+    if point in pooled:
+        return point - 1, [([(pooled[point], 0, None)], True)], True
+    if point == 15:
+        return 14, [([("conv6_1_CPM", 0, 128)], True), ([("conv6_2_CPM", 0, 512)], False)], False
+    s, i = 2 + (point - 16) // 6, (point - 16) % 6
+    if i == 0:
+        sel = np.concatenate([np.arange(C), cpm_heat_channels(net) + np.arange(128)]).astype(np.int64)
+        return point - 1, [([("Mconv1_stage%d" % s, sel, None)], True)], False
+    if i < 5:
+        return point - 1, [([("Mconv%d_stage%d" % (i + 1, s), 0, 128)], True)], False
+    return point - 1, [([("Mconv6_stage%d" % s, 0, 128)], True), ([("Mconv7_stage%d" % s, 0, 128)], False)], False
+
+
+def point_spec(point, net="posenet"):
     """-> (input point, steps, pooled).  steps: [(groups, relu)], groups: [(layer, c0, c1)] = the layer
-    reads input channels [c0, c1) and the groups' outputs are concatenated.  The map points' steps give
-    the 57 (paf | heat) channels; the probe appends the 128 feature channels (a copy of point 11)."""
+    reads input channels [c0, c1) (c0 an index array: those channels) and the groups' outputs are
+    concatenated.  The map points' steps give the 57 (paf | heat) channels (C heat channels for the
+    CPM nets); the probe appends the 128 feature channels (a copy of point 11; 14 for the CPM nets,
+    behind the heat slice's zero padding)."""
+    if net not in NETS:
+        raise ValueError("net: one of %s" % (NETS,))
     if not 1 <= point < N_POINTS:
         raise ValueError("point 1 .. 45")
+    if net != "posenet":
+        return _cpm_point_spec(point, net)
     one = {2: "conv2_1", 4: "conv3_1", 5: "conv3_2", 6: "conv3_3", 8: "conv4_1", 9: "conv4_2", 10: "conv4_3_CPM",
            11: "conv4_4_CPM"}
     pooled = {3: "conv2_2", 7: "conv3_4"}
@@ -100,14 +147,18 @@ def point_spec(point):
                        ([("Mconv7_stage%d_L1" % s, 0, 128), ("Mconv7_stage%d_L2" % s, 128, 256)], False)], False
 
 
-def out_channels(point, weights):
-    """Channels the point's layers write (57 at the map points, without the feature copy)."""
-    groups = point_spec(point)[1][-1][0]
+def out_channels(point, weights, net="posenet"):
+    """Channels the point's layers write (57, or C, at the map points, without the feature copy)."""
+    groups = point_spec(point, net)[1][-1][0]
     return sum(weights[name][0].shape[0] for name, _, _ in groups)
 
 
 class _Run(object):
-    def __init__(self, precision, inputs, weights, mode, conv11, mutate, reverse=False):
+    def __init__(self, precision, inputs, weights, mode, conv11, mutate, reverse=False, net="posenet", inputs_hi=None):
+        self.net = net
+        # the hi halves of the stored input pairs (bf16x3): the operands are then (hi, inputs - hi) and a
+        # fused group's intermediate keeps the pair the kernel makes, instead of split(hi + lo)
+        self.x_hi = None if inputs_hi is None else np.ascontiguousarray(inputs_hi, dtype=np.float32)
         if precision not in ("fp32", "bf16x3"):
             raise ValueError("precision: 'fp32' or 'bf16x3'")
         if conv11 not in ("mfma", "f32"):
@@ -121,7 +172,18 @@ class _Run(object):
         self.reverse = reverse
 
 
-def _gemm_ideal(run, name, xg, W, b, last):
+def _operands(xm, xm_hi):
+    """The (hi, lo) pair of the activations: the stored one where its hi halves are known, else split()
+    of hi + lo -- the same pair unless hi + lo lies exactly halfway between two bf16 values (0.1 % of
+    the stored values): the kernel that stored it rounded its f32 value, which was off the tie, to
+    either neighbour and lo to minus or plus half a step, and split() of the sum always takes the even
+    one.  The three products differ between the two pairs by w_lo times one bf16 step of x."""
+    if xm_hi is None:
+        return split(xm)
+    return xm_hi, xm - xm_hi  # exact: lo is a bf16 value
+
+
+def _gemm_ideal(run, name, xg, W, b, last, xg_hi=None):
     """xg (P, taps, Ci) f32, W (taps, Ci, Co) f32 -> (P, Co) float64."""
     P = xg.shape[0]
     K = W.shape[0] * W.shape[1]
@@ -131,7 +193,7 @@ def _gemm_ideal(run, name, xg, W, b, last):
     exact = (not run.split) or (name == "conv1_1" and run.conv11 == "f32")
     if exact:
         return xm.astype(np.float64) @ Wm.astype(np.float64) + bias
-    x_hi, x_lo = split(xm)
+    x_hi, x_lo = _operands(xm, None if xg_hi is None else xg_hi.reshape(P, K))
     w_hi, w_lo = split(Wm)
     x_hi, x_lo, w_hi, w_lo = (a.astype(np.float64) for a in (x_hi, x_lo, w_hi, w_lo))
     drop = run.mutate.get("drop") if last else None
@@ -148,32 +210,57 @@ def _gemm_ideal(run, name, xg, W, b, last):
     return y + bias
 
 
-def _kernel_channel_order(xg, W):
-    """The 185-channel stage input in the order the kernels walk it: a 192-channel pixel with the
+def _physical_channels(net, name, ci):
+    """src[p] = the logical input channel of `name` at physical channel p of the tensor the kernels
+    walk, -1 for channel padding; None where the two orders are the same.
+    posenet (185 channels): feature at 0..127, heat at 128..146, paf at 152..189 of 192 (csrc/common.hpp
+    kCatFeat / kCatHeat / kCatPaf; weights.hip cat_logical).  CPM Mconv1 (C + 128 channels): feature at
+    0..127, heat at 128..128+C-1 of 128 + C rounded up to 16 (csrc/cpm.hip op_cpm_set_weights cmap):
+    feature chunks 0..7, then the heat chunks; 9 of the 16 channels of facenet's 13th chunk are padding."""
+    if net == "posenet":
+        if ci != 185:
+            return None
+        src = np.full(192, -1, np.int64)
+        src[0:128] = np.arange(57, 185)
+        src[128:147] = np.arange(38, 57)
+        src[152:190] = np.arange(0, 38)
+        return src
+    C = CPM_MAPS[net]
+    if not name.startswith("Mconv1_") or ci != C + 128:
+        return None
+    src = np.full(128 + cpm_heat_channels(net), -1, np.int64)
+    src[0:128] = C + np.arange(128)
+    src[128:128 + C] = np.arange(C)
+    return src
+
+
+def _kernel_channel_order(run, name, xg, W):
+    """The stage input in the order the kernels walk it (_physical_channels), zeros at the padding.
+    posenet: the 185-channel stage input in the order the kernels walk it: a 192-channel pixel with the
     feature at 0..127, heat at 128..146 and paf at 152..189, zeros between (csrc/common.hpp kCatFeat /
     kCatHeat / kCatPaf; weights.hip cat_logical packs Mconv1's weights the same way).  The order is
     part of the yardstick: measured on the GPU in fp32, Mconv1's error has the r.m.s. of the
     sequential sum in this order, 25 % above that of the (paf, heat, feature) order."""
-    if xg.shape[2] != 185:
+    src = _physical_channels(run.net, name, xg.shape[2])
+    if src is None:
         return xg, W
-    src = np.full(192, -1, np.int64)
-    src[0:128] = np.arange(57, 185)
-    src[128:147] = np.arange(38, 57)
-    src[152:190] = np.arange(0, 38)
-    xp = np.zeros(xg.shape[:2] + (192,), xg.dtype)
-    Wp = np.zeros((W.shape[0], 192, W.shape[2]), W.dtype)
+    xp = np.zeros(xg.shape[:2] + (len(src),), xg.dtype)
+    Wp = np.zeros((W.shape[0], len(src), W.shape[2]), W.dtype)
     xp[:, :, src >= 0] = xg[:, :, src[src >= 0]]
     Wp[:, src >= 0] = W[:, src[src >= 0]]
     return xp, Wp
 
 
-def _gemm_seq(run, name, xg, W, b):
+def _gemm_seq(run, name, xg, W, b, xg_hi=None):
     """The same terms in float32, one at a time: 16-channel chunk, tap, product, channel.  A bf16 x
     bf16 product is exact in float32, so only the adds round; on the exact paths every term is one
     fused multiply-add (the float64 product of two float32 is exact)."""
-    xg, W = _kernel_channel_order(xg, W)
+    if xg_hi is not None:
+        xg_hi = _kernel_channel_order(run, name, xg_hi, W)[0]
+    xg, W = _kernel_channel_order(run, name, xg, W)
     if run.reverse:  # the channels walked backwards: the same sum in another order
         xg, W = xg[:, :, ::-1], W[:, ::-1]
+        xg_hi = None if xg_hi is None else xg_hi[:, :, ::-1]
     P, taps, Ci = xg.shape
     Co = W.shape[2]
     acc = np.zeros((P, Co), np.float32)
@@ -185,7 +272,7 @@ def _gemm_seq(run, name, xg, W, b):
                 for ci in range(c0, min(c0 + 16, Ci)):
                     acc = (acc + x64[:, t, ci, None] * w64[t, ci][None, :]).astype(np.float32)
         return (acc + b.astype(np.float32)[None, :]).astype(np.float64)
-    x_hi, x_lo = split(xg)
+    x_hi, x_lo = _operands(xg, xg_hi)
     w_hi, w_lo = split(W)
     for c0 in range(0, Ci, 16):
         c1 = min(c0 + 16, Ci)
@@ -213,39 +300,58 @@ def _eval(run, steps, k, pix):
     code = (pix[:, 0, None] * H + np.where(inside, ny, 0)) * Wd + np.where(inside, nx, 0)
     uniq, inv = np.unique(code[inside], return_inverse=True)
     upix = np.stack([uniq // (H * Wd), (uniq // Wd) % H, uniq % Wd], axis=1)
+    prev_hi = None
     if k == 0:
         prev = run.x[upix[:, 0], :, upix[:, 1], upix[:, 2]]  # (U, C) f32
+        if run.x_hi is not None and run.split:
+            prev_hi = run.x_hi[upix[:, 0], :, upix[:, 1], upix[:, 2]]
     else:
         prev = _eval(run, steps, k - 1, upix).astype(np.float32)  # the kernel's f32 value ...
         if run.split:
+            if run.x_hi is not None:
+                prev_hi = bf16_rne(prev)  # (the pair the kernel makes of it)
             prev = recon(prev)  # ... kept as its hi/lo pair
     prev = np.concatenate([prev, np.zeros((1, prev.shape[1]), np.float32)], axis=0)  # row U: zero padding
+    if prev_hi is not None:
+        prev_hi = np.concatenate([prev_hi, np.zeros((1, prev_hi.shape[1]), np.float32)], axis=0)
     idx = np.full(code.shape, len(uniq), np.int64)
     idx[inside] = inv
     out = []
     for name, c0, c1 in groups:
         Wl, b = run.w[name]
         Wt = np.ascontiguousarray(np.asarray(Wl, np.float32).transpose(2, 3, 1, 0)).reshape(ks * ks, Wl.shape[1], Wl.shape[0])
-        pg = prev[:, c0:c1]
+        pg = prev[:, c0] if isinstance(c0, np.ndarray) else prev[:, c0:c1]
+        pg_hi = None if prev_hi is None else (prev_hi[:, c0] if isinstance(c0, np.ndarray) else prev_hi[:, c0:c1])
         ys = []
         blk = max(1, (32 << 20) // (ks * ks * pg.shape[1] * 4))
         for p0 in range(0, P, blk):
             xg = pg[idx[p0:p0 + blk]]  # (p, taps, Ci)
+            xg_hi = None if pg_hi is None else pg_hi[idx[p0:p0 + blk]]
             if last and "chunk" in run.mutate:
                 pi, tap, c16 = run.mutate["chunk"]
-                if p0 <= pi < p0 + blk and c0 <= 16 * c16 < (c1 if c1 is not None else 1 << 30):
+                if run.net != "posenet":  # the CPM nets: chunk c16 of the physical order
+                    phys = _physical_channels(run.net, name, xg.shape[2])
+                    lost = (phys if phys is not None else np.arange(xg.shape[2]))[16 * c16:16 * c16 + 16]
+                    if p0 <= pi < p0 + blk:
+                        xg = xg.copy()
+                        xg[pi - p0, tap, lost[lost >= 0]] = 0
+                        if xg_hi is not None:
+                            xg_hi = xg_hi.copy()
+                            xg_hi[pi - p0, tap, lost[lost >= 0]] = 0
+                elif p0 <= pi < p0 + blk and c0 <= 16 * c16 < (c1 if c1 is not None else 1 << 30):
                     xg = xg.copy()
                     xg[pi - p0, tap, 16 * c16 - c0:16 * c16 - c0 + 16] = 0
             b = np.asarray(b, np.float32)
-            ys.append(_gemm_seq(run, name, xg, Wt, b) if run.seq else _gemm_ideal(run, name, xg, Wt, b, last))
+            ys.append(_gemm_seq(run, name, xg, Wt, b, xg_hi) if run.seq else _gemm_ideal(run, name, xg, Wt, b, last, xg_hi))
         out.append(np.concatenate(ys, axis=0))
     y = np.concatenate(out, axis=1)
     return np.maximum(y, 0.0) if relu else y
 
 
-def _evaluate(point, precision, inputs, weights, pixels, mode, conv11, mutate, reverse=False):
-    run = _Run(precision, inputs, weights, mode, conv11, mutate, reverse)
-    _, steps, pooled = point_spec(point)
+def _evaluate(point, precision, inputs, weights, pixels, mode, conv11, mutate, reverse=False, net="posenet",
+              inputs_hi=None):
+    run = _Run(precision, inputs, weights, mode, conv11, mutate, reverse, net, inputs_hi)
+    _, steps, pooled = point_spec(point, net)
     pix = np.asarray(pixels, np.int64).reshape(-1, 3)
     if not pooled:
         return _eval(run, steps, len(steps) - 1, pix)
@@ -256,21 +362,27 @@ def _evaluate(point, precision, inputs, weights, pixels, mode, conv11, mutate, r
     return np.maximum(np.maximum(quad[0], quad[1]), np.maximum(quad[2], quad[3]))
 
 
-def ideal(point, precision, inputs, weights, pixels, conv11="mfma", mutate=None):
+def ideal(point, precision, inputs, weights, pixels, conv11="mfma", mutate=None, net="posenet", inputs_hi=None):
     """The float64 ideal of probe point `point` at output pixels `pixels` ((P, 3): frame, y, x of the
     point's output map) from `inputs` (frames, C, H, W): the probed tensor of point_spec(point)[0] (its
     first C channels are read; a map point's 185 are what Mconv1 reads).  -> (P, channels) float64.
     mutate (the sensitivity tests): {"drop": "w_lo*x_hi" | "w_hi*x_lo"}, {"shift": 1} (the patch one
-    column to the right), {"chunk": (pixel index, tap, 16-channel chunk)} (those products lost)."""
-    return _evaluate(point, precision, inputs, weights, pixels, "ideal", conv11, mutate)
+    column to the right), {"chunk": (pixel index, tap, 16-channel chunk)} (those products lost; for the
+    CPM nets the chunk of the physical channel order, _physical_channels).
+    net "facenet" / "handnet": the points of op_cpm_forward_probe; a map point's tensor is [heat C |
+    zero pad | feature 128] as probed, of which Mconv1 reads the (heat C, feature 128) channels.
+    inputs_hi (bf16x3): the hi halves of the stored input pairs, as the probe returns them on request
+    (_operands says why hi + lo alone is not enough); with them a fused group's intermediate also
+    keeps the kernel's own pair.  Without, every pair is split() of the value."""
+    return _evaluate(point, precision, inputs, weights, pixels, "ideal", conv11, mutate, net=net, inputs_hi=inputs_hi)
 
 
-def seq_f32(point, precision, inputs, weights, pixels, conv11="mfma", reverse=False):
+def seq_f32(point, precision, inputs, weights, pixels, conv11="mfma", reverse=False, net="posenet", inputs_hi=None):
     """The same terms as ideal() accumulated in float32 one at a time (16-channel chunk, tap, product,
     channel order), fused groups composed the same way: the accumulation-error yardstick.  reverse:
     the channels walked backwards, i.e. another correct accumulation (tests/test_layer_ref.py holds
     the yardstick to it)."""
-    return _evaluate(point, precision, inputs, weights, pixels, "seq", conv11, None, reverse)
+    return _evaluate(point, precision, inputs, weights, pixels, "seq", conv11, None, reverse, net, inputs_hi)
 
 
 def all_pixels(frames, h, w):
@@ -284,20 +396,26 @@ def to_nchw(values, frames, h, w):
     return np.ascontiguousarray(values.reshape(frames, h, w, -1).transpose(0, 3, 1, 2))
 
 
-def walk(weights, x, precision, upto, conv11="mfma"):
+def walk(weights, x, precision, upto, conv11="mfma", net="posenet"):
     """{point: (frames, C, h, w) float32} for points 0 .. upto: every point's ideal at every pixel from
     the previous point's stored result (float32; its hi + lo in bf16x3), the map points with the
-    feature copy appended -- tensors with the statistics of the probed ones, for the CPU tests."""
+    feature copy appended (for the CPM nets behind the heat slice's zero padding, as probed) -- tensors
+    with the statistics of the probed ones, for the CPU tests."""
     x = np.ascontiguousarray(x, dtype=np.float32)
     acts = {0: recon(x) if precision == "bf16x3" else x}
     for p in range(1, upto + 1):
-        src, _, pooled = point_spec(p)
+        src, _, pooled = point_spec(p, net)
         inp = acts[src]
         F, _, H, W = inp.shape
         oh, ow = (H // 2, W // 2) if pooled else (H, W)
-        y = ideal(p, precision, inp, weights, all_pixels(F, oh, ow), conv11).astype(np.float32)
+        y = ideal(p, precision, inp, weights, all_pixels(F, oh, ow), conv11, net=net).astype(np.float32)
         y = to_nchw(recon(y) if precision == "bf16x3" else y, F, oh, ow)
-        acts[p] = np.concatenate([y, acts[11]], axis=1) if p in MAP_POINTS else y
+        if p in MAP_POINTS and net != "posenet":
+            pad = np.zeros((F, cpm_heat_channels(net) - y.shape[1], oh, ow), np.float32)
+            y = np.concatenate([y, pad, acts[CPM_FEATURE_POINT]], axis=1)
+        elif p in MAP_POINTS:
+            y = np.concatenate([y, acts[11]], axis=1)
+        acts[p] = y
     return acts
 
 

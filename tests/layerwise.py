@@ -82,18 +82,19 @@ def checked_pixels(n_batch, frames, h, w, rng):
     return np.stack([f, y, x], axis=1).astype(np.int64)
 
 
-def compare(point, precision, conv11, weights, inp, out, n_batch):
+def compare(point, precision, conv11, weights, inp, out, n_batch, net="posenet", inp_hi=None):
     """One probe point against its reference.  inp / out: the probed input and output tensors (the
-    first 57 channels of a map point).  -> dict(max_err, e_seq, ratio = max |err| / e_seq, need = the
+    first 57 channels of a map point; net "facenet" / "handnet": the first C, tests/cpm_layerwise.py;
+    inp_hi: the hi halves of the input's stored pairs, layer_ref.ideal's inputs_hi).  -> dict(max_err, e_seq, ratio = max |err| / e_seq, need = the
     factor on e_seq the point needs once the output rounding r |ideal| is taken off (the test allows
     2), worst = the largest |err| / tolerance with its (frame, channel, y, x), n = outputs checked)."""
     frames, ch, h, w = out.shape
     rng = np.random.default_rng(point)
     pix = checked_pixels(n_batch, frames, h, w, rng)
-    want = R.ideal(point, precision, inp, weights, pix, conv11)
+    want = R.ideal(point, precision, inp, weights, pix, conv11, net=net, inputs_hi=inp_hi)
     assert want.shape == (len(pix), ch), (want.shape, out.shape)
-    sample = R.yardstick_pixels(want, weights[R.point_spec(point)[1][-1][0][0][0]][0].shape[2], rng)
-    seq = R.seq_f32(point, precision, inp, weights, pix[sample], conv11)
+    sample = R.yardstick_pixels(want, weights[R.point_spec(point, net)[1][-1][0][0][0]][0].shape[2], rng)
+    seq = R.seq_f32(point, precision, inp, weights, pix[sample], conv11, net=net, inputs_hi=inp_hi)
     e_seq = float(np.abs(seq - want[sample]).max())
     got = out[pix[:, 0], :, pix[:, 1], pix[:, 2]].astype(np.float64)
     err = np.abs(got - want)

@@ -79,6 +79,34 @@ def test_probe_table_follows_the_layer_table(lib):
     assert len({t[0] for t in table}) == len(table)
 
 
+@pytest.mark.parametrize("arch", ["facenet", "handnet"])
+def test_cpm_probe_table_follows_the_layer_table(lib, arch):
+    """op_cpm_probe_info (host only): 46 points per net; a point's channels are what its last layer
+    writes (oracle/layer_ref.py point_spec(net=) walks the same launches); the map points return the
+    padded heat slice of the stage buffer (128 + C rounded up to 16, less 128) and the 128 feature
+    channels."""
+    from oracle import layer_ref
+    table = lib.cpm_probe_table(arch)
+    co = {name: c for name, _, c, _ in lib.cpm_layer_table(arch)}
+    heat = layer_ref.cpm_heat_channels(arch)
+    assert heat == {"facenet": 80, "handnet": 32}[arch] and co["Mconv7_stage6"] == layer_ref.CPM_MAPS[arch]
+    assert len(table) == layer_ref.N_POINTS and table[0] == ("input", 3, 1) and table[45] == ("stage6", heat + 128, 8)
+    for point in range(1, len(table)):
+        src, steps, pooled = layer_ref.point_spec(point, arch)
+        want = sum(co[name] for name, _, _ in steps[-1][0])
+        if point in layer_ref.MAP_POINTS:
+            want = heat + 128
+        else:
+            assert table[point][0].split("+")[0] == steps[-1][0][0][0], table[point]
+        assert table[point][1] == want, (point, table[point])
+        assert table[point][2] == table[src][2] * (2 if pooled else 1), (point, table[point])
+    assert len({t[0] for t in table}) == len(table)
+    name, ch, div = ctypes.c_char_p(), ctypes.c_int32(), ctypes.c_int32()
+    for a, point in ((lib.ARCH[arch], -1), (lib.ARCH[arch], 46), (0, 3), (3, 3)):
+        assert lib.lib().op_cpm_probe_info(a, point, ctypes.byref(name), ctypes.byref(ch), ctypes.byref(div)) == lib.OP_ERR_INVALID
+    assert lib.lib().op_cpm_probe_info(lib.ARCH[arch], 3, None, ctypes.byref(ch), ctypes.byref(div)) == lib.OP_ERR_INVALID
+
+
 def test_train_buffer_table_follows_the_layer_table(lib):
     """op_train_buffer_info (host only): OP_TRAIN_BUFFERS buffers; every layer but the map writers and
     conv4_4_CPM (which write into the stage inputs / stage-6 maps) names the buffer it writes, with its
