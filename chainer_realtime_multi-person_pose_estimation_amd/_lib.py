@@ -40,6 +40,7 @@ EXPORTED = (
     "op_train_buffer_info", "op_train_read_buffer",
     "op_augment", "op_augment_last_ms", "op_augment_last_paths", "op_augment_tables",
     "op_ignore_masks", "op_ignore_masks_last_ms",
+    "op_draw", "op_draw_staged", "op_staged_info", "op_draw_last_ms",
 )
 ARCH = {"facenet": 1, "handnet": 2}
 CPM_PROBE_HI = 256  # OP_CPM_PROBE_HI
@@ -71,6 +72,17 @@ class OpFrameResult(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
         "status", "n_peaks", "n_persons", "map_w", "map_h", "net_w", "net_h")]
 
+
+class OpDrawPrim(ctypes.Structure):
+    """op_draw_prim (include/openpose_hip.h): one primitive of a display list (render.py)."""
+    _fields_ = [("kind", ctypes.c_int32), ("radius", ctypes.c_int32),
+                ("x0", ctypes.c_double), ("y0", ctypes.c_double), ("x1", ctypes.c_double), ("y1", ctypes.c_double),
+                ("thickness", ctypes.c_double),
+                ("wa", ctypes.c_double), ("wb", ctypes.c_double), ("gamma", ctypes.c_double),
+                ("bgr", ctypes.c_uint8 * 3), ("pad", ctypes.c_uint8 * 5)]
+
+
+OP_DRAW_LINE, OP_DRAW_DISC, OP_DRAW_BLEND = range(3)
 
 _lib = None
 
@@ -178,6 +190,10 @@ def lib():
         "op_augment_tables": ([P, P, P, P], ctypes.c_int),
         "op_ignore_masks": ([I32, I32, P, P, P, P, P, P, P, P, P, P, P], ctypes.c_int),
         "op_ignore_masks_last_ms": ([I32, P], ctypes.c_int),
+        "op_draw": ([I32, I32, P, P, P, P, P, P], ctypes.c_int),
+        "op_draw_staged": ([P, I32, I32, P, P, P], ctypes.c_int),
+        "op_staged_info": ([P, P, P, P], ctypes.c_int),
+        "op_draw_last_ms": ([I32, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -629,6 +645,12 @@ class Context(object):
 
     def use_staged_maps(self, enable):
         check(lib().op_use_staged_maps(self.h, 1 if enable else 0))
+
+    def staged_info(self):
+        """(n, h, w) of the staged frame set, (0, 0, 0) when nothing is staged (op_staged_info)."""
+        v = [ctypes.c_int32() for _ in range(3)]
+        check(lib().op_staged_info(self.h, *[ctypes.byref(x) for x in v]), "op_staged_info")
+        return tuple(x.value for x in v)
 
     def run_staged(self, graph=False):
         check((lib().op_run_staged_graph if graph else lib().op_run_staged)(self.h), "op_run_staged")

@@ -35,13 +35,17 @@ def draw_rectangle(img, p0, p1, color):
         draw_line(img, a, b, color, 1)
 
 
-def run(img, pose_detector, face_detector, hand_detector, log=print):
+def run(img, pose_detector, face_detector, hand_detector, log=print, device_draw=False):
     """demo.py:20-56.  The crops of every person are detected in two batched forwards (faces,
     hands: ``detect_batch``) and drawn in the reference's per-person order, so the image is the
-    same as with one detector call per crop."""
+    same as with one detector call per crop.  ``device_draw``: the same drawing as one display
+    list in one device call (render.demo_list, render.render); the image is the same bit for bit."""
     log("Estimating pose...")
     person_pose_array, _ = pose_detector(img)
-    res_img = add_weighted(img, 0.6, draw_person_pose(img, person_pose_array), 0.4, 0)
+    if device_draw:  # the poses as they are drawn: crop_hands below shifts the hand joints in place
+        drawn_poses = np.array(person_pose_array, copy=True)
+    else:
+        res_img = add_weighted(img, 0.6, draw_person_pose(img, person_pose_array), 0.4, 0)
     faces, hands = [], []
     for person_pose in person_pose_array:
         unit_length = pose_detector.get_unit_length(person_pose)
@@ -52,6 +56,17 @@ def run(img, pose_detector, face_detector, hand_detector, log=print):
     face_kps = iter(face_detector.detect_batch(face_crops) if face_crops else [])
     hand_kps = iter(hand_detector.detect_batch([c for c, _ in hand_crops], [s for _, s in hand_crops])
                     if hand_crops else [])
+    if device_draw:
+        from . import render
+        face_items, hand_items = [], []
+        for (cropped_face_img, bbox), person_hands in zip(faces, hands):
+            log("Estimating face keypoints...")
+            face_items.append((next(face_kps), bbox) if cropped_face_img is not None else None)
+            log("Estimating hands keypoints...")
+            hand_items.append({side: (next(hand_kps), person_hands[side]["bbox"]) if person_hands[side] is not None
+                               else None for side in ("left", "right")})
+        prims = render.demo_list(drawn_poses, face_items, hand_items)
+        return render.render([img], [prims], device=pose_detector.device)[0]
     for (cropped_face_img, bbox), person_hands in zip(faces, hands):
         log("Estimating face keypoints...")
         if cropped_face_img is not None:
@@ -73,6 +88,7 @@ def main(argv=None):
     ap.add_argument("--models", default="models", help="directory of coco_posenet.npz / handnet.npz / facenet.npz")
     ap.add_argument("--random-weights", action="store_true", help="seeded random weights (plumbing run)")
     ap.add_argument("--out", default="result.png")
+    ap.add_argument("--device-draw", action="store_true", help="draw on the device (one display list, one launch)")
     args = ap.parse_args(argv)
     if args.random_weights:
         pd = PoseDetector("posenet", model=_weights.random_weights(0), device=args.gpu)
@@ -83,7 +99,7 @@ def main(argv=None):
         hd = HandDetector("handnet", os.path.join(args.models, "handnet.npz"), device=args.gpu)
         fd = FaceDetector("facenet", os.path.join(args.models, "facenet.npz"), device=args.gpu)
     img = read_bgr(args.img)
-    res_img = run(img, pd, fd, hd)
+    res_img = run(img, pd, fd, hd, device_draw=args.device_draw)
     print("Saving result into %s..." % args.out)
     write_bgr(args.out, res_img)
     return 0

@@ -108,11 +108,16 @@ def main(argv=None):
     ap.add_argument("--gpu", "-g", type=int, default=-1, help="HIP device (negative: device 0; no CPU path)")
     ap.add_argument("--precise", action="store_true", help="do precise inference")
     ap.add_argument("--out", default="result.png", help="output image path")
+    ap.add_argument("--device-draw", action="store_true", help="draw on the device (render.render), the same image")
     args = ap.parse_args(argv)
     det = PoseDetector(args.arch, args.weights, device=args.gpu, precise=args.precise)
     img = read_bgr(args.img)
     poses, _ = det(img)
-    img = draw_person_pose(img, poses)
+    if args.device_draw:
+        from . import render
+        img = render.render([img], [render.pose_list(poses)], device=det.device)[0]
+    else:
+        img = draw_person_pose(img, poses)
     print("Saving result into %s..." % args.out)
     write_bgr(args.out, img)
     return 0

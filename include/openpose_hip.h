@@ -644,6 +644,57 @@ int op_ignore_masks(int32_t device, int32_t n, const int32_t* hw, const int32_t*
  * completed on `device`; OP_ERR_STATE before the first. */
 int op_ignore_masks_last_ms(int32_t device, double* ms);
 
+/* ---- Skeleton overlays from a display list (draw.py draw_line / draw_disc, demo.py add_weighted) ----
+ * One primitive of a frame's display list (render.py builds the lists on the host).  A frame's
+ * primitives are painted in order, a later one over an earlier one:
+ *   OP_DRAW_LINE  the pixels of draw.draw_line((x0, y0), (x1, y1), bgr, thickness): inside the box
+ *                 floor(min(x0, x1) - r) .. ceil(max(x0, x1) + r) (y alike, r = thickness / 2) and
+ *                 within r of the segment, in draw.py's float64 operations, one rounding each;
+ *   OP_DRAW_DISC  the pixels of draw.draw_disc((x0, y0), radius, bgr): integer centre (x0, y0),
+ *                 dx * dx + dy * dy <= radius * radius;
+ *   OP_DRAW_BLEND at most one per frame: the picture so far becomes
+ *                 saturate_u8(rint(input * wa + picture * wb + gamma)) (demo.add_weighted: float64,
+ *                 summed left to right, rint to even); the primitives after it paint over the blend.
+ * Fields a kind does not use are not read. */
+#define OP_DRAW_LINE 0
+#define OP_DRAW_DISC 1
+#define OP_DRAW_BLEND 2
+typedef struct op_draw_prim {
+  int32_t kind;
+  int32_t radius;        /* DISC: 0 .. 1024 */
+  double x0, y0, x1, y1; /* LINE: end points; DISC: the centre in (x0, y0), whole numbers */
+  double thickness;      /* LINE: > 0 */
+  double wa, wb, gamma;  /* BLEND */
+  uint8_t bgr[3];        /* LINE, DISC */
+  uint8_t pad[5];
+} op_draw_prim;
+/* A batch of n frames of any sizes on `device`: bgr[f] is frame f's hw[2f] x hw[2f + 1] (h, w) x 3 u8
+ * image with row_stride[f] bytes per row, its list prims[prim_offsets[f] .. prim_offsets[f + 1] - 1]
+ * (it may be empty), out[f] a host pointer to h * w * 3 u8.  One kernel launch for the whole batch,
+ * one workgroup per 64 x 16 pixel tile of a frame; the result is render.py's render_np bit for bit
+ * (draw.py's rasteriser stays unpinned against OpenCV's).
+ * Arguments are validated before any device call (OP_ERR_INVALID, the message names the field): null
+ * arrays or entries, n < 1, h or w outside 1 .. 16384, a row stride below 3 w, offsets that do not
+ * start at 0 or decrease, an unknown kind, a coordinate that is not finite or above 32768 in
+ * magnitude (every integer product of the line test is then exact in float64 and the box fits
+ * int32), a disc centre that is not a whole number, a thickness that is not in (0, 32768], a radius
+ * outside 0 .. 1024, more than one BLEND in a frame's list, blend weights that are not finite. */
+int op_draw(int32_t device, int32_t n, const uint8_t* const* bgr, const int64_t* row_stride, const int32_t* hw,
+            const int32_t* prim_offsets, const op_draw_prim* prims, uint8_t* const* out);
+/* The same kernel on staged frames [first, first + n) of ctx (op_stage_frames, or the frames an
+ * op_run_staged* took from op_upload_frames; an upload no run has taken yet is not drawn on), read in
+ * place: no second upload, and the staged frames are not modified.  Frame first + f owns the list
+ * prims[prim_offsets[f] .. prim_offsets[f + 1] - 1]; out is n * h * w * 3 u8 on the host.  The kernel
+ * runs on the context stream, behind a queued op_run_staged*; the call returns when out is filled.
+ * Validation as for op_draw, and a range outside the staged set; OP_ERR_STATE when nothing is staged. */
+int op_draw_staged(op_ctx* ctx, int32_t first, int32_t n, const int32_t* prim_offsets, const op_draw_prim* prims,
+                   uint8_t* out);
+/* The staged frame set op_draw_staged reads: *n frames of *h x *w (all 0 when nothing is staged). */
+int op_staged_info(op_ctx* ctx, int32_t* n, int32_t* h, int32_t* w);
+/* Device time (ms, stream events) of the uploads and the kernel of the last op_draw or
+ * op_draw_staged that completed on `device`; OP_ERR_STATE before the first. */
+int op_draw_last_ms(int32_t device, double* ms);
+
 #ifdef __cplusplus
 }
 #endif
