@@ -33,6 +33,7 @@ EXPORTED = (
     "op_cpm_layer_count", "op_cpm_layer_info", "op_cpm_create", "op_cpm_destroy", "op_cpm_set_weights",
     "op_cpm_forward", "op_cpm_peaks", "op_cpm_detect", "op_cpm_detect_batch", "op_cpm_set_batch_invariant",
     "op_cpm_probe_info", "op_cpm_forward_probe",
+    "op_cpm_detect_rois", "op_cpm_set_roi_group_bytes", "op_cpm_roi_stats",
     "op_train_create", "op_train_destroy", "op_train_set_weights", "op_train_get_weights", "op_train_set_hyper",
     "op_train_enable_layer", "op_train_set_grad_scale", "op_train_step",
     "op_make_labels", "op_train_step_poses", "op_train_last_label_ms",
@@ -167,6 +168,9 @@ def lib():
         "op_host_free": ([P], ctypes.c_int),
         "op_fetch_maps": ([P, I32, I32, P, P, P, P], ctypes.c_int),
         "op_cpm_set_batch_invariant": ([P, I32], ctypes.c_int),
+        "op_cpm_detect_rois": ([P, I32, P, P, P, P, I32, P, P, P, ctypes.c_float, P, P], ctypes.c_int),
+        "op_cpm_set_roi_group_bytes": ([P, I64], ctypes.c_int),
+        "op_cpm_roi_stats": ([P, P], ctypes.c_int),
         "op_train_create": ([I32, I32, I32, I32, P], ctypes.c_int),
         "op_train_destroy": ([P], ctypes.c_int),
         "op_train_set_weights": ([P, P, P], ctypes.c_int),
@@ -914,6 +918,57 @@ class CpmContext(object):
         check(lib().op_cpm_detect_batch(self.h, n, ptrs, ptr(hs), ptr(ws), ptr(rs), float(thresh), ptr(fl), ptr(kp),
                                         ptr(found)), "op_cpm_detect_batch")
         return [self._keypoints(kp[i], found[i]) for i in range(n)]
+
+    ROI_GROUP_LAUNCHES = 4  # kRoiGroupLaunches (csrc/cpm.hip): post-process launches per group
+
+    @staticmethod
+    def roi_table_bytes(n_frames, n_rois):
+        """Bytes of the device tables one ``detect_rois`` call uploads (include/openpose_hip.h)."""
+        return 24 * int(n_frames) + 48 * int(n_rois)
+
+    def detect_rois(self, frames, boxes, thresh, frame_ids=None, mirror=None):
+        """``detect_batch`` fed from frames and integer boxes (op_cpm_detect_rois): box i =
+        (left, top, right, bottom) of ``frames[frame_ids[i]]`` (default: frame 0), read mirrored in x
+        where ``mirror[i]`` (default: none).  The crop (roi_crop_np states it), the mirror, the
+        resize, the forward, the upsample and the peaks run on the device; each frame is uploaded
+        once.  ``frames``: one H x W x 3 uint8 image or a list of them.  The keypoints of
+        ``detect_batch([roi_crop_np(...)], thresh, flip_maps=mirror)``, bit for bit."""
+        if isinstance(frames, np.ndarray) and frames.ndim == 3:
+            frames = [frames]
+        imgs = [_row_strided_u8(f) for f in frames]
+        for img in imgs:
+            if img.ndim != 3 or img.shape[2] != 3:
+                raise ValueError("expected H x W x 3 uint8 BGR frames")
+        n, nf, np_ = len(boxes), len(imgs), self.n_maps - 1
+        if n == 0:
+            return []
+        bx = np.ascontiguousarray(np.asarray(boxes, np.int64).reshape(n, 4))
+        if np.any(np.abs(bx) > 2 ** 31 - 1):
+            raise ValueError("op_cpm_detect_rois: box coordinates must fit int32")
+        bx = bx.astype(np.int32)
+        fi = np.zeros(n, np.int32) if frame_ids is None else np.ascontiguousarray(frame_ids, np.int32)
+        mi = np.zeros(n, np.int32) if mirror is None else np.array([int(bool(m)) for m in mirror], np.int32)
+        if len(fi) != n or len(mi) != n:
+            raise ValueError("frame_ids and mirror need one entry per box")
+        ptrs = (ctypes.c_void_p * max(nf, 1))(*[img.ctypes.data for img in imgs])
+        hs = np.array([img.shape[0] for img in imgs], np.int32)
+        ws = np.array([img.shape[1] for img in imgs], np.int32)
+        rs = np.array([img.strides[0] for img in imgs], np.int64)
+        kp = np.zeros((n, np_, 3), np.float64)
+        found = np.zeros((n, np_), np.int32)
+        check(lib().op_cpm_detect_rois(self.h, nf, ptrs, ptr(hs), ptr(ws), ptr(rs), n, ptr(fi), ptr(bx), ptr(mi),
+                                       float(thresh), ptr(kp), ptr(found)), "op_cpm_detect_rois")
+        return [self._keypoints(kp[i], found[i]) for i in range(n)]
+
+    def set_roi_group_bytes(self, nbytes=0):
+        """Scratch budget of one post-process group of ``detect_rois`` (0: the default)."""
+        check(lib().op_cpm_set_roi_group_bytes(self.h, int(nbytes)), "op_cpm_set_roi_group_bytes")
+
+    def roi_stats(self):
+        """The last ``detect_rois``: {groups, launches (outside the forward), upload_bytes, scratch_bytes}."""
+        out = np.zeros(4, np.int64)
+        check(lib().op_cpm_roi_stats(self.h, ptr(out)), "op_cpm_roi_stats")
+        return dict(zip(("groups", "launches", "upload_bytes", "scratch_bytes"), (int(v) for v in out)))
 
 
 class TrainContext(object):

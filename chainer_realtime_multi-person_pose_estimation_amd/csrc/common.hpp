@@ -187,6 +187,44 @@ int launch_split_to_planar(const float* in, float* out, int32_t n, int32_t h, in
                            int32_t c16, hipStream_t st);
 int launch_preprocess_split(const uint8_t* frames, int64_t frame_bytes, int64_t row_stride, int32_t n, int32_t sh,
                             int32_t sw, int32_t dh, int32_t dw, float* out, hipStream_t st, float div = 255.0f);
+// ---- ROI detection (op_cpm_detect_rois): the device tables of one call, written by the host after
+// it validated every field the kernels index with ----
+struct RoiFrame {  // one uploaded frame: rows packed, `stride` bytes apart, `base` bytes into the frame arena
+  int64_t base, stride;
+  int32_t h, w;
+};
+struct RoiSrc {  // one ROI: the virtual bh x bw crop whose (y, x) is frame[t + y][l + (mirror ? bw-1-x : x)]
+  int32_t frame, l, t, bw, bh, mirror;
+};
+struct RoiPlane {  // one ROI's full-size planes within its group's scratch
+  int64_t off;     // first float of its planes (np planes of h x w)
+  int32_t h, w;
+  int32_t blk0;    // first 256-thread block of the ROI in its group's per-element launches
+  int32_t mirror;  // argmax reads the planes x-mirrored
+};
+// network input of every ROI in one launch: slot i of `out` (n x (dh+2) x (dw+2) x 16 split) from
+// ROI i's virtual crop, the arithmetic and stores of launch_preprocess_split on that crop
+int launch_preprocess_split_rois(const uint8_t* frames, const RoiFrame* d_frames, const RoiSrc* d_rois, int32_t n,
+                                 int32_t dh, int32_t dw, float* out, hipStream_t st, float div);
+// launch_resize_images for ROIs [r0, r0 + cnt) of the table in one launch: the first c planes of the
+// dense f32 maps `maps` ((n, h, w, cs), ROI i = frame i) -> the ROI's planes in `y`; `blocks` = the
+// group's block count (RoiPlane::blk0 of a ROI behind the last)
+int launch_resize_rois(const float* maps, int32_t cs, int32_t c, int32_t h, int32_t w, const RoiPlane* d_planes,
+                       int32_t r0, int32_t cnt, int64_t blocks, float* y, hipStream_t st);
+// The ROI of the group [r0, r0 + cnt) that owns block `b` of a per-element launch: the last whose
+// blk0 <= b (blk0 ascends from 0, so the result is in [r0, r0 + cnt) for any b >= 0).
+__device__ __forceinline__ int roi_of_block(const RoiPlane* __restrict__ T, int r0, int cnt, int b) {
+  int lo = 0, hi = cnt - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (T[r0 + mid].blk0 <= b)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  return r0 + lo;
+}
+
 int launch_extract_maps32(const float* m, int32_t cs, int32_t heat_off, int32_t n, int32_t h, int32_t w, float* paf,
                           float* heat, hipStream_t st);
 // An activation tensor as op_forward_probe's extraction reads it (ctx.hpp Act): fmt 0 f32

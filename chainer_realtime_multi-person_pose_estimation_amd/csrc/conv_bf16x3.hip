@@ -430,6 +430,66 @@ int launch_preprocess_split(const uint8_t* frames, int64_t frame_bytes, int64_t 
   return OP_OK;
 }
 
+// The virtual crop of one ROI as cv_linear_px_from's image: crop (y, x) is frame (t + y, l + x), or
+// (t + y, l + bw-1-x) mirrored; 0 outside the frame (PoseDetector.crop_image, then [:, ::-1]).
+struct RoiCropRows {
+  const uint8_t* frame;
+  int64_t stride;
+  int fh, fw, l, t, bw, mirror;
+  struct Row {
+    const uint8_t* p;  // the frame row, or null above / below the frame
+    int fw, l, bw, mirror;
+    __device__ __forceinline__ int at(int x, int ch) const {
+      const int fx = l + (mirror ? bw - 1 - x : x);
+      return p && fx >= 0 && fx < fw ? (int)p[fx * 3 + ch] : 0;
+    }
+  };
+  __device__ __forceinline__ Row row(int r) const {
+    const int fy = t + r;
+    return Row{fy >= 0 && fy < fh ? frame + (int64_t)fy * stride : nullptr, fw, l, bw, mirror};
+  }
+};
+
+// preprocess_split16 over ROIs of device-resident frames: blocks [roi * bpr, (roi + 1) * bpr) write
+// slot roi, so a block reads one table entry (block-uniform) and its lanes take consecutive pixels
+__global__ __launch_bounds__(256) void preprocess_split16_rois(const uint8_t* __restrict__ frames,
+                                                               const RoiFrame* __restrict__ ftab,
+                                                               const RoiSrc* __restrict__ rtab, int bpr, int dh, int dw,
+                                                               char* __restrict__ out, float div) {
+  const int wp = dw + 2, hp = dh + 2;
+  const int roi = blockIdx.x / bpr;
+  const int i = (blockIdx.x - roi * bpr) * 256 + threadIdx.x;  // pixel of the slot
+  if (i >= hp * wp) return;
+  const RoiSrc r = rtab[roi];
+  const RoiFrame f = ftab[r.frame];
+  const int px = i % wp, py = i / wp;
+  float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const int dy = py - 1, dx = px - 1;
+  if (dy >= 0 && dy < dh && dx >= 0 && dx < dw) {
+    const RoiCropRows img{frames + f.base, f.stride, f.h, f.w, r.l, r.t, r.bw, r.mirror};
+    const LinTap tx = cv_linear_tap(dx, dw, r.bw, true);  // cv_linear_norm's taps
+    const LinTap ty = cv_linear_tap(dy, dh, r.bh, false);
+    for (int c = 0; c < 3; ++c) v[c] = cv_linear_px_from(img, r.bh, r.bw, tx, ty, c, div);
+  }
+  char* o = out + ((int64_t)roi * hp * wp + i) * 64;
+  store_split8(o, v);
+  store_split8(o + 32, z);
+}
+
+int launch_preprocess_split_rois(const uint8_t* frames, const RoiFrame* d_frames, const RoiSrc* d_rois, int32_t n,
+                                 int32_t dh, int32_t dw, float* out, hipStream_t st, float div) {
+  const int bpr = ((dh + 2) * (dw + 2) + 255) / 256;
+  if (n < 1 || (int64_t)bpr * n > 0x7fffffffll) {
+    set_error("preprocess_split16_rois: bad ROI count");
+    return OP_ERR_INVALID;
+  }
+  hipLaunchKernelGGL(preprocess_split16_rois, dim3((unsigned)(bpr * n)), dim3(256), 0, st, frames, d_frames, d_rois,
+                     bpr, dh, dw, (char*)out, div);
+  OP_AFTER_LAUNCH("preprocess_split16_rois", st);
+  OP_HIP_CHECK(hipGetLastError());
+  return OP_OK;
+}
+
 // f32 maps (n, lh, lw, cs) dense (paf at 0, heat at heat_off) -> planar (n,38,h,w), (n,19,h,w).
 __global__ __launch_bounds__(256) void extract_maps32(const float* __restrict__ m, int cs, int heat_off, int n, int h,
                                                       int w, float* __restrict__ paf, float* __restrict__ heat) {

@@ -15,6 +15,12 @@
 //   passes in SciPy's order with an f32 store between them (the pose path's arithmetic), then per
 //   map one workgroup finds the max and the first two maxima in (optionally x-mirrored) row-major
 //   order = np.where's order, from which the host forms [coords[1], coords[0], max].
+// ROI detection (op_cpm_detect_rois): the same detector fed with frames and integer boxes.  Each
+//   frame is uploaded once; preprocess_split16_rois cuts, mirrors and resizes every ROI's virtual
+//   crop into its input slot in one launch; after the one forward, consecutive ROIs share a group
+//   under a scratch budget and each group takes kRoiGroupLaunches launches over ROIs of different
+//   sizes (resize_planar_rois, cpm_gauss_rois<true|false>, cpm_argmax_rois: the arithmetic of the
+//   per-crop kernels, shared with them); one copy brings every argmax record back.
 #include <cstring>
 #include <string>
 #include <vector>
@@ -94,8 +100,20 @@ __device__ __forceinline__ int scipy_reflect(int i, int L) {  // mode='reflect' 
   return i >= L ? p - 1 - i : i;
 }
 
-// one SciPy correlate1d pass (NI_Correlate1D symmetric: centre tap, then pairs outermost first,
-// f64) along y (VERT) or x over the first `c` planes of (c, h, w); f32 result
+// one output of a SciPy correlate1d pass (NI_Correlate1D symmetric: centre tap, then pairs outermost
+// first, f64) along y (VERT) or x at (y, x) of the h x w plane p; f32 result
+template <bool VERT>
+__device__ __forceinline__ float cpm_gauss_at(const float* __restrict__ p, int y, int x, int h, int w,
+                                              const double* __restrict__ wt, int r) {
+  auto at = [&](int d) -> double {
+    return VERT ? (double)p[(int64_t)scipy_reflect(y + d, h) * w + x] : (double)p[(int64_t)y * w + scipy_reflect(x + d, w)];
+  };
+  double o = __dmul_rn(at(0), wt[r]);
+  for (int jj = -r; jj < 0; ++jj) o = __dadd_rn(o, __dmul_rn(__dadd_rn(at(jj), at(-jj)), wt[r + jj]));
+  return __double2float_rn(o);
+}
+
+// one correlate1d pass over the first `c` planes of (c, h, w)
 template <bool VERT>
 __global__ __launch_bounds__(256) void cpm_gauss(const float* __restrict__ in, int c, int h, int w,
                                                  const double* __restrict__ wt, int r, float* __restrict__ out) {
@@ -104,24 +122,33 @@ __global__ __launch_bounds__(256) void cpm_gauss(const float* __restrict__ in, i
   if (i >= plane * c) return;
   const int x = (int)(i % w);
   const int y = (int)((i / w) % h);
-  const float* p = in + (i / plane) * plane;
-  auto at = [&](int d) -> double {
-    return VERT ? (double)p[(int64_t)scipy_reflect(y + d, h) * w + x] : (double)p[(int64_t)y * w + scipy_reflect(x + d, w)];
-  };
-  double o = __dmul_rn(at(0), wt[r]);
-  for (int jj = -r; jj < 0; ++jj) o = __dadd_rn(o, __dmul_rn(__dadd_rn(at(jj), at(-jj)), wt[r + jj]));
-  out[i] = __double2float_rn(o);
+  out[i] = cpm_gauss_at<VERT>(in + (i / plane) * plane, y, x, h, w, wt, r);
+}
+
+// cpm_gauss over the `c` planes of every ROI of the group [r0, r0 + cnt) in one launch: the block's
+// ROI from roi_of_block (once per block), lanes on consecutive x
+template <bool VERT>
+__global__ __launch_bounds__(256) void cpm_gauss_rois(const float* __restrict__ in, int c,
+                                                      const RoiPlane* __restrict__ tab, int r0, int cnt,
+                                                      const double* __restrict__ wt, int r, float* __restrict__ out) {
+  const RoiPlane e = tab[roi_of_block(tab, r0, cnt, (int)blockIdx.x)];
+  const int h = e.h, w = e.w;
+  const int64_t i = (int64_t)((int)blockIdx.x - e.blk0) * 256 + threadIdx.x;
+  const int64_t plane = (int64_t)h * w;
+  if (i >= plane * c) return;
+  const int x = (int)(i % w);
+  const int y = (int)((i / w) % h);
+  out[e.off + i] = cpm_gauss_at<VERT>(in + e.off + (i / plane) * plane, y, x, h, w, wt, r);
 }
 
 // per plane: max, number of maxima, first two maxima in row-major order of the (x-mirrored if
 // flip) plane.  res[4 * plane] = {max bits, count, idx0, idx1}
 constexpr int kArgT = 1024;
-__global__ __launch_bounds__(kArgT) void cpm_argmax(const float* __restrict__ filt, int h, int w, int flip,
-                                                    int32_t* __restrict__ res) {
+__device__ __forceinline__ void cpm_argmax_plane(const float* __restrict__ p, int h, int w, int flip,
+                                                 int32_t* __restrict__ res) {
   __shared__ float smax[kArgT / 64];
   __shared__ int scnt[kArgT / 64], s0[kArgT / 64], s1[kArgT / 64];
   const int64_t plane = (int64_t)h * w;
-  const float* p = filt + blockIdx.x * plane;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   float m = -INFINITY;
   for (int64_t i = threadIdx.x; i < plane; i += kArgT) m = fmaxf(m, p[i]);
@@ -166,12 +193,32 @@ __global__ __launch_bounds__(kArgT) void cpm_argmax(const float* __restrict__ fi
       b = min(hi, min(b, s1[k]));
       a = lo;
     }
-    res[4 * blockIdx.x + 0] = __float_as_int(m);
-    res[4 * blockIdx.x + 1] = c;
-    res[4 * blockIdx.x + 2] = a;
-    res[4 * blockIdx.x + 3] = b;
+    res[0] = __float_as_int(m);
+    res[1] = c;
+    res[2] = a;
+    res[3] = b;
   }
 }
+
+__global__ __launch_bounds__(kArgT) void cpm_argmax(const float* __restrict__ filt, int h, int w, int flip,
+                                                    int32_t* __restrict__ res) {
+  cpm_argmax_plane(filt + blockIdx.x * ((int64_t)h * w), h, w, flip, res + 4 * blockIdx.x);
+}
+
+// cpm_argmax over the `c` planes of every ROI of the group [r0, r0 + cnt): block b takes plane b % c
+// of ROI r0 + b / c and writes record (r0 + b / c) * c + b % c
+__global__ __launch_bounds__(kArgT) void cpm_argmax_rois(const float* __restrict__ filt, int c,
+                                                         const RoiPlane* __restrict__ tab, int r0,
+                                                         int32_t* __restrict__ res) {
+  const int j = r0 + (int)blockIdx.x / c, pl = (int)blockIdx.x % c;
+  const RoiPlane e = tab[j];
+  cpm_argmax_plane(filt + e.off + pl * ((int64_t)e.h * e.w), e.h, e.w, e.mirror, res + 4 * ((int64_t)j * c + pl));
+}
+
+// op_cpm_detect_rois: launches per post-process group (upsample, Gaussian along y, Gaussian along
+// x, argmax) and the default scratch budget of a group (its two full-size plane sets)
+constexpr int kRoiGroupLaunches = 4;
+constexpr int64_t kRoiGroupBytes = 256ll << 20;
 
 }  // namespace op
 
@@ -194,6 +241,12 @@ struct op_cpm_ctx {
   double* d_gauss = nullptr;
   int gauss_r = 0;
   int splitk = 1;  // op_cpm_set_batch_invariant(0): small launches may split K (batch-dependent sums)
+  // op_cpm_detect_rois: scratch budget of one post-process group, the host image of the last call's
+  // device tables (alive until that call's copies have run) and its op_cpm_roi_stats
+  int64_t roi_group_bytes = kRoiGroupBytes;
+  std::vector<char> roi_tables;
+  bool roi_pending = false;
+  int64_t roi_stats[4] = {0, 0, 0, 0};
 };
 
 namespace op {
@@ -847,6 +900,181 @@ int op_cpm_detect_batch(op_cpm_ctx* c, int32_t n, const uint8_t* const* bgr, con
   for (int i = 0; i < n; ++i)
     cpm_peaks_decode(res.data() + (size_t)i * np * 4, ch, w[i], thresh, keypoints + (size_t)i * np * 3,
                      found + (size_t)i * np);
+  return OP_OK;
+}
+
+// ---- ROI detection: crops, mirror, resize, forward, upsample and peaks from frames and boxes ----
+
+// What op_cpm_detect_rois lays out on the host before it launches anything: the three device
+// tables (one image, uploaded once) and the post-process groups.
+struct RoiGroup {
+  int r0, cnt;
+  int64_t blocks, floats;  // of its per-element launches; of one plane set
+};
+struct RoiPlan {
+  std::vector<RoiGroup> groups;
+  std::vector<int64_t> frame_off;  // per frame: bytes into the frame arena
+  int64_t frame_arena = 0, frame_packed = 0, group_floats = 0;
+  size_t frames_at = 0, rois_at = 0, planes_at = 0;  // byte offsets of the tables in the image
+};
+
+// Validates every argument the kernels will index with (OP_ERR_INVALID naming the frame or ROI) and
+// fills *plan and *tables; makes no HIP call.  planes: full-size planes per ROI (maps - 1).
+static int cpm_rois_pack(int32_t n_frames, const uint8_t* const* bgr, const int32_t* fh, const int32_t* fw,
+                         const int64_t* row_stride, int32_t n, const int32_t* roi_frame, const int32_t* roi_box,
+                         const int32_t* roi_mirror, int planes, int64_t budget, RoiPlan* plan,
+                         std::vector<char>* tables) {
+  const char* who = "op_cpm_detect_rois: ";
+  if (n_frames < 1 || !bgr || !fh || !fw || !row_stride || !roi_frame || !roi_box) {
+    set_error(std::string(who) + "bad arguments");
+    return OP_ERR_INVALID;
+  }
+  auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
+  std::vector<RoiFrame> F(n_frames);
+  plan->frame_off.resize(n_frames);
+  for (int f = 0; f < n_frames; ++f) {
+    // 3 * w and every x * 3 + ch of a row stay within int32
+    if (!bgr[f] || fh[f] < 1 || fw[f] < 1 || fw[f] > 0x7fffffff / 3 || row_stride[f] < (int64_t)fw[f] * 3) {
+      set_error(std::string(who) + "bad frame " + std::to_string(f));
+      return OP_ERR_INVALID;
+    }
+    const int64_t packed = (int64_t)fw[f] * 3;
+    F[f] = RoiFrame{plan->frame_arena, packed, fh[f], fw[f]};
+    plan->frame_off[f] = plan->frame_arena;
+    plan->frame_arena += al(packed * fh[f]);
+    plan->frame_packed += packed * fh[f];
+  }
+  constexpr int64_t kCoord = 1ll << 30;
+  std::vector<RoiSrc> R(n);
+  std::vector<RoiPlane> P(n);
+  RoiGroup g{0, 0, 0, 0};
+  for (int i = 0; i < n; ++i) {
+    const int32_t* b = roi_box + 4 * (size_t)i;
+    bool ok = roi_frame[i] >= 0 && roi_frame[i] < n_frames;
+    for (int k = 0; k < 4; ++k) ok = ok && b[k] >= -kCoord && b[k] <= kCoord;
+    const int64_t bw = (int64_t)b[2] - b[0], bh = (int64_t)b[3] - b[1];
+    ok = ok && bw >= 2 && bh >= 2 && bw * bh < (1ll << 31);
+    if (!ok) {
+      set_error(std::string(who) + "bad ROI " + std::to_string(i));
+      return OP_ERR_INVALID;
+    }
+    const int mirror = roi_mirror && roi_mirror[i] ? 1 : 0;
+    R[i] = RoiSrc{roi_frame[i], b[0], b[1], (int32_t)bw, (int32_t)bh, mirror};
+    const int64_t elems = (int64_t)planes * bw * bh;
+    const int64_t floats = (elems + 63) / 64 * 64, blocks = (elems + 255) / 256;
+    // a group holds two plane sets (f32) within the budget and its launches within one grid; a ROI
+    // that exceeds the budget alone is a group of its own
+    if (g.cnt > 0 && ((g.floats + floats) * 8 > budget || g.blocks + blocks > 0x7fffffffll)) {
+      plan->groups.push_back(g);
+      g = RoiGroup{i, 0, 0, 0};
+    }
+    P[i] = RoiPlane{g.floats, (int32_t)bh, (int32_t)bw, (int32_t)g.blocks, mirror};
+    g.cnt += 1;
+    g.floats += floats;
+    g.blocks += blocks;
+    plan->group_floats = std::max(plan->group_floats, g.floats);
+  }
+  plan->groups.push_back(g);
+  plan->frames_at = 0;
+  plan->rois_at = F.size() * sizeof(RoiFrame);
+  plan->planes_at = plan->rois_at + R.size() * sizeof(RoiSrc);
+  tables->resize(plan->planes_at + P.size() * sizeof(RoiPlane));
+  memcpy(tables->data() + plan->frames_at, F.data(), F.size() * sizeof(RoiFrame));
+  memcpy(tables->data() + plan->rois_at, R.data(), R.size() * sizeof(RoiSrc));
+  memcpy(tables->data() + plan->planes_at, P.data(), P.size() * sizeof(RoiPlane));
+  return OP_OK;
+}
+
+int op_cpm_set_roi_group_bytes(op_cpm_ctx* c, int64_t bytes) {
+  CRC(cpm_check(c, false));
+  if (bytes < 0) {
+    set_error("op_cpm_set_roi_group_bytes: negative budget");
+    return OP_ERR_INVALID;
+  }
+  c->roi_group_bytes = bytes ? bytes : kRoiGroupBytes;
+  return OP_OK;
+}
+
+int op_cpm_roi_stats(op_cpm_ctx* c, int64_t out[4]) {
+  CRC(cpm_check(c, false));
+  if (!out) {
+    set_error("op_cpm_roi_stats: null out");
+    return OP_ERR_INVALID;
+  }
+  for (int k = 0; k < 4; ++k) out[k] = c->roi_stats[k];
+  return OP_OK;
+}
+
+int op_cpm_detect_rois(op_cpm_ctx* c, int32_t n_frames, const uint8_t* const* bgr, const int32_t* fh,
+                       const int32_t* fw, const int64_t* row_stride, int32_t n, const int32_t* roi_frame,
+                       const int32_t* roi_box, const int32_t* roi_mirror, float thresh, double* keypoints,
+                       int32_t* found) {
+  CRC(cpm_check(c, true));
+  if (n < 0 || (n > 0 && (!keypoints || !found))) {
+    set_error("op_cpm_detect_rois: bad arguments");
+    return OP_ERR_INVALID;
+  }
+  if (n == 0) return OP_OK;
+  static_assert(sizeof(RoiFrame) == 24 && sizeof(RoiSrc) == 24 && sizeof(RoiPlane) == 24, "device table layout");
+  const int S = 368;  // as op_cpm_detect
+  const int lh = S / 8, lw = S / 8, ch = c->nm, np = ch - 1;
+  if (c->roi_pending) {  // a call that failed midway: its table image may still be the source of a copy
+    OP_HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->roi_pending = false;
+  }
+  RoiPlan plan;
+  CRC(cpm_rois_pack(n_frames, bgr, fh, fw, row_stride, n, roi_frame, roi_box, roi_mirror, np, c->roi_group_bytes, &plan,
+                    &c->roi_tables));
+  CRC(cpm_geometry(c, n, S, S));
+  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+  // scratch: the frames, the tables, the argmax records, two full-size plane sets of one group
+  const size_t tab_off = (size_t)plan.frame_arena, res_off = tab_off + al(c->roi_tables.size());
+  const size_t pa_off = res_off + al((size_t)n * np * 16), pb = al((size_t)plan.group_floats * 4);
+  const size_t total = pa_off + 2 * pb;
+  CRC(cpm_scratch(c, total));
+  char* s = (char*)c->scratch;
+  c->roi_pending = true;
+  for (int f = 0; f < n_frames; ++f) {
+    const int64_t packed = (int64_t)fw[f] * 3;
+    OP_HIP_CHECK(hipMemcpy2DAsync(s + plan.frame_off[f], packed, bgr[f], row_stride[f], packed, fh[f],
+                                  hipMemcpyHostToDevice, c->stream));
+  }
+  OP_HIP_CHECK(hipMemcpyAsync(s + tab_off, c->roi_tables.data(), c->roi_tables.size(), hipMemcpyHostToDevice, c->stream));
+  const RoiFrame* d_frames = (const RoiFrame*)(s + tab_off + plan.frames_at);
+  const RoiSrc* d_rois = (const RoiSrc*)(s + tab_off + plan.rois_at);
+  const RoiPlane* d_planes = (const RoiPlane*)(s + tab_off + plan.planes_at);
+  int64_t launches = 1;
+  CRC(launch_preprocess_split_rois((const uint8_t*)s, d_frames, d_rois, n, S, S, c->buf[X0].p, c->stream, 256.0f));
+  CRC(cpm_run(c));
+  float* pa = (float*)(s + pa_off);  // upsampled maps, then the filtered ones
+  float* pt = (float*)(s + pa_off + pb);
+  int32_t* dres = (int32_t*)(s + res_off);
+  for (const RoiGroup& g : plan.groups) {
+    CRC(launch_resize_rois(c->buf[MAP32].p, c->buf[MAP32].cs, np, lh, lw, d_planes, g.r0, g.cnt, g.blocks, pa,
+                           c->stream));
+    hipLaunchKernelGGL(cpm_gauss_rois<true>, dim3((unsigned)g.blocks), dim3(256), 0, c->stream, pa, np, d_planes, g.r0,
+                       g.cnt, c->d_gauss, c->gauss_r, pt);
+    OP_AFTER_LAUNCH("cpm_gauss_rois_v", c->stream);
+    hipLaunchKernelGGL(cpm_gauss_rois<false>, dim3((unsigned)g.blocks), dim3(256), 0, c->stream, pt, np, d_planes, g.r0,
+                       g.cnt, c->d_gauss, c->gauss_r, pa);
+    OP_AFTER_LAUNCH("cpm_gauss_rois_h", c->stream);
+    hipLaunchKernelGGL(cpm_argmax_rois, dim3((unsigned)(g.cnt * np)), dim3(kArgT), 0, c->stream, pa, np, d_planes, g.r0,
+                       dres);
+    OP_AFTER_LAUNCH("cpm_argmax_rois", c->stream);
+    OP_HIP_CHECK(hipGetLastError());
+    launches += kRoiGroupLaunches;
+  }
+  std::vector<int32_t> res((size_t)n * np * 4);
+  OP_HIP_CHECK(hipMemcpyAsync(res.data(), dres, res.size() * 4, hipMemcpyDeviceToHost, c->stream));
+  OP_HIP_CHECK(hipStreamSynchronize(c->stream));
+  c->roi_pending = false;
+  for (int i = 0; i < n; ++i)
+    cpm_peaks_decode(res.data() + (size_t)i * np * 4, ch, roi_box[4 * (size_t)i + 2] - roi_box[4 * (size_t)i],
+                     thresh, keypoints + (size_t)i * np * 3, found + (size_t)i * np);
+  c->roi_stats[0] = (int64_t)plan.groups.size();
+  c->roi_stats[1] = launches;
+  c->roi_stats[2] = plan.frame_packed + (int64_t)c->roi_tables.size();
+  c->roi_stats[3] = (int64_t)total;
   return OP_OK;
 }
 

@@ -111,6 +111,28 @@ __global__ __launch_bounds__(256) void resize_planar(const float* __restrict__ x
                     p[(t.v0 + 1) * w + t.u0 + 1]);
 }
 
+// resize_planar for a group of ROIs of different sizes in one launch: block b belongs to the ROI
+// roi_of_block finds (once per block); its lanes take consecutive x of the ROI's (c, oh, ow) planes.
+// The source is ROI j's frame of the dense f32 maps (n, h, w, cs): plane cc's (v, u) is
+// x[((j * h + v) * w + u) * cs + cc], the value resize_planar reads from the planar copy.
+__global__ __launch_bounds__(256) void resize_planar_rois(const float* __restrict__ x, int cs, int c, int h, int w,
+                                                          const RoiPlane* __restrict__ tab, int r0, int cnt,
+                                                          float* __restrict__ y) {
+  const int j = roi_of_block(tab, r0, cnt, (int)blockIdx.x);
+  const RoiPlane e = tab[j];
+  const int oh = e.h, ow = e.w;
+  const int64_t plane = (int64_t)oh * ow;
+  const int64_t i = (int64_t)((int)blockIdx.x - e.blk0) * 256 + threadIdx.x;
+  if (i >= plane * c) return;
+  const int ox = (int)(i % ow);
+  const int oy = (int)((i / ow) % oh);
+  const int cc = (int)(i / plane);
+  const UpTap t = up_tap(oy, ox, h, w, oh, ow);
+  const float* p = x + (int64_t)j * h * w * cs + cc;
+  y[e.off + i] = up_combine(t, p[(t.v0 * w + t.u0) * cs], p[(t.v0 * w + t.u0 + 1) * cs],
+                            p[((t.v0 + 1) * w + t.u0) * cs], p[((t.v0 + 1) * w + t.u0 + 1) * cs]);
+}
+
 // PAF sample at map pixel (y, x) of PAF channel c: recomputed from the low-res map with the
 // upsample formula (identical f32 value to the full-res map the reference indexes), or read from a
 // full-res planar map (stage-level ABI).
@@ -1319,6 +1341,19 @@ int launch_resize_images(const float* x, int32_t c, int32_t h, int32_t w, int32_
                          hipStream_t st) {
   hipLaunchKernelGGL(resize_planar, dim3(nblk((int64_t)c * oh * ow)), dim3(256), 0, st, x, c, h, w, oh, ow, y);
   OP_AFTER_LAUNCH("resize_planar", st);
+  OP_HIP_CHECK(hipGetLastError());
+  return OP_OK;
+}
+
+int launch_resize_rois(const float* maps, int32_t cs, int32_t c, int32_t h, int32_t w, const RoiPlane* d_planes,
+                       int32_t r0, int32_t cnt, int64_t blocks, float* y, hipStream_t st) {
+  if (cnt < 1 || c < 1 || h < 2 || w < 2 || blocks < 1 || blocks > 0x7fffffffll) {
+    set_error("resize_planar_rois: bad group");
+    return OP_ERR_INVALID;
+  }
+  hipLaunchKernelGGL(resize_planar_rois, dim3((unsigned)blocks), dim3(256), 0, st, maps, cs, c, h, w, d_planes, r0, cnt,
+                     y);
+  OP_AFTER_LAUNCH("resize_planar_rois", st);
   OP_HIP_CHECK(hipGetLastError());
   return OP_OK;
 }

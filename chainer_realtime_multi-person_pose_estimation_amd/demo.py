@@ -35,11 +35,14 @@ def draw_rectangle(img, p0, p1, color):
         draw_line(img, a, b, color, 1)
 
 
-def run(img, pose_detector, face_detector, hand_detector, log=print, device_draw=False):
+def run(img, pose_detector, face_detector, hand_detector, log=print, device_draw=False, device_crops=False):
     """demo.py:20-56.  The crops of every person are detected in two batched forwards (faces,
     hands: ``detect_batch``) and drawn in the reference's per-person order, so the image is the
     same as with one detector call per crop.  ``device_draw``: the same drawing as one display
-    list in one device call (render.demo_list, render.render); the image is the same bit for bit."""
+    list in one device call (render.demo_list, render.render); the image is the same bit for bit.
+    ``device_crops``: the detectors get the image and the boxes (PoseDetector.face_bbox /
+    hand_bboxes, one ``detect_rois`` call each) and cut, mirror and resize the crops on the
+    device; the keypoints, and so the image, are the same bit for bit."""
     log("Estimating pose...")
     person_pose_array, _ = pose_detector(img)
     if device_draw:  # the poses as they are drawn: crop_hands below shifts the hand joints in place
@@ -47,15 +50,29 @@ def run(img, pose_detector, face_detector, hand_detector, log=print, device_draw
     else:
         res_img = add_weighted(img, 0.6, draw_person_pose(img, person_pose_array), 0.4, 0)
     faces, hands = [], []
-    for person_pose in person_pose_array:
-        unit_length = pose_detector.get_unit_length(person_pose)
-        faces.append(pose_detector.crop_face(img, person_pose, unit_length))
-        hands.append(pose_detector.crop_hands(img, person_pose, unit_length))
-    face_crops = [f[0] for f in faces if f[0] is not None]
-    hand_crops = [(h[side]["img"], side) for h in hands for side in ("left", "right") if h[side] is not None]
-    face_kps = iter(face_detector.detect_batch(face_crops) if face_crops else [])
-    hand_kps = iter(hand_detector.detect_batch([c for c, _ in hand_crops], [s for _, s in hand_crops])
-                    if hand_crops else [])
+    if device_crops:
+        # boxes only: (True, bbox) / {"bbox": bbox} stand where the default path holds the crops
+        for person_pose in person_pose_array:
+            unit_length = pose_detector.get_unit_length(person_pose)
+            bbox = pose_detector.face_bbox(person_pose, unit_length)
+            faces.append((None, None) if bbox is None else (True, bbox))
+            boxes = pose_detector.hand_bboxes(person_pose, unit_length)
+            hands.append({side: None if boxes[side] is None else {"bbox": boxes[side]} for side in ("left", "right")})
+        face_boxes = [f[1] for f in faces if f[0] is not None]
+        hand_boxes = [(h[side]["bbox"], side) for h in hands for side in ("left", "right") if h[side] is not None]
+        face_kps = iter(face_detector.detect_rois(img, face_boxes) if face_boxes else [])
+        hand_kps = iter(hand_detector.detect_rois(img, [b for b, _ in hand_boxes], [s for _, s in hand_boxes])
+                        if hand_boxes else [])
+    else:
+        for person_pose in person_pose_array:
+            unit_length = pose_detector.get_unit_length(person_pose)
+            faces.append(pose_detector.crop_face(img, person_pose, unit_length))
+            hands.append(pose_detector.crop_hands(img, person_pose, unit_length))
+        face_crops = [f[0] for f in faces if f[0] is not None]
+        hand_crops = [(h[side]["img"], side) for h in hands for side in ("left", "right") if h[side] is not None]
+        face_kps = iter(face_detector.detect_batch(face_crops) if face_crops else [])
+        hand_kps = iter(hand_detector.detect_batch([c for c, _ in hand_crops], [s for _, s in hand_crops])
+                        if hand_crops else [])
     if device_draw:
         from . import render
         face_items, hand_items = [], []
@@ -89,6 +106,8 @@ def main(argv=None):
     ap.add_argument("--random-weights", action="store_true", help="seeded random weights (plumbing run)")
     ap.add_argument("--out", default="result.png")
     ap.add_argument("--device-draw", action="store_true", help="draw on the device (one display list, one launch)")
+    ap.add_argument("--device-crops", action="store_true",
+                    help="cut the face / hand crops on the device from the image and the boxes (detect_rois)")
     args = ap.parse_args(argv)
     if args.random_weights:
         pd = PoseDetector("posenet", model=_weights.random_weights(0), device=args.gpu)
@@ -99,7 +118,7 @@ def main(argv=None):
         hd = HandDetector("handnet", os.path.join(args.models, "handnet.npz"), device=args.gpu)
         fd = FaceDetector("facenet", os.path.join(args.models, "facenet.npz"), device=args.gpu)
     img = read_bgr(args.img)
-    res_img = run(img, pd, fd, hd, device_draw=args.device_draw)
+    res_img = run(img, pd, fd, hd, device_draw=args.device_draw, device_crops=args.device_crops)
     print("Saving result into %s..." % args.out)
     write_bgr(args.out, res_img)
     return 0

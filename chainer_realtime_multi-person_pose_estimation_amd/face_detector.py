@@ -17,6 +17,23 @@ from .constants import params
 from .draw import draw_disc, draw_line
 
 
+def roi_crop_np(frame, bbox, mirror=False):
+    """The virtual crop ``detect_rois`` cuts on the device, stated in NumPy: pixel (y, x) of the
+    (bottom-top) x (right-left) crop is ``frame[top + y][left + x]``, or
+    ``frame[top + y][left + (right-left-1-x)]`` when ``mirror``; 0 where that point lies outside the
+    frame.  Equal to ``PoseDetector.crop_image(frame, bbox)`` (then ``[:, ::-1]``)."""
+    frame = np.asarray(frame)
+    left, top, right, bottom = (int(v) for v in bbox)
+    h, w = frame.shape[:2]
+    ys = top + np.arange(bottom - top)
+    xs = left + np.arange(right - left)
+    if mirror:
+        xs = xs[::-1]
+    inside = ((ys >= 0) & (ys < h))[:, None] & ((xs >= 0) & (xs < w))[None, :]
+    px = frame[np.clip(ys, 0, h - 1)[:, None], np.clip(xs, 0, w - 1)[None, :]]
+    return np.where(inside[:, :, None], px, 0).astype(np.uint8)
+
+
 class FaceDetector(object):
     def __init__(self, arch=None, weights_file=None, model=None, device=-1):
         arch = arch or "facenet"
@@ -49,6 +66,12 @@ class FaceDetector(object):
     def detect_batch(self, face_imgs):
         """``__call__`` over many crops in one batched forward (op_cpm_detect_batch)."""
         return self._ctx.detect_batch(face_imgs, params["face_heatmap_peak_thresh"])
+
+    def detect_rois(self, imgs, bboxes, frame_ids=None):
+        """``detect_batch`` on the boxes ``bboxes`` (left, top, right, bottom) of the frame(s)
+        ``imgs`` (one image, or a list with ``frame_ids[i]`` naming box i's): the crops are cut on
+        the device (op_cpm_detect_rois, roi_crop_np), each frame is uploaded once."""
+        return self._ctx.detect_rois(imgs, bboxes, params["face_heatmap_peak_thresh"], frame_ids=frame_ids)
 
 
 def draw_face_keypoints(orig_img, face_keypoints, left_top):

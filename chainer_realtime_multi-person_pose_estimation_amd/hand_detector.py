@@ -53,6 +53,13 @@ class HandDetector(object):
         imgs = [np.ascontiguousarray(np.asarray(im)[:, ::-1]) if lf else im for im, lf in zip(hand_imgs, lefts)]
         return self._ctx.detect_batch(imgs, params["hand_heatmap_peak_thresh"], flip_maps=lefts)
 
+    def detect_rois(self, imgs, bboxes, hand_types, frame_ids=None):
+        """``detect_batch`` on the boxes ``bboxes`` (left, top, right, bottom) of the frame(s)
+        ``imgs``: the crops are cut on the device (op_cpm_detect_rois, face_detector.roi_crop_np) and
+        a ``"left"`` box is read mirrored there, so no host crop or flip is made."""
+        return self._ctx.detect_rois(imgs, bboxes, params["hand_heatmap_peak_thresh"], frame_ids=frame_ids,
+                                     mirror=[t == "left" for t in hand_types])
+
 
 def draw_hand_keypoints(orig_img, hand_keypoints, left_top):
     """hand_detector.py:96-116: per finger, radius-3 discs on both ends and a 1-px line."""

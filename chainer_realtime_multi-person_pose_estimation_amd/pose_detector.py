@@ -207,19 +207,25 @@ class PoseDetector(object):
         every call raises NameError there; this mirror raises the same error."""
         raise NameError("name 'sys' is not defined")
 
-    def crop_face(self, img, person_pose, unit_length):
-        """pose_detector.py:354-369: (face_img, bbox) from 1.2 units above to 0.8 below the nose and
-        one unit either side of it, or (None, None) without a nose."""
+    def face_bbox(self, person_pose, unit_length):
+        """The bbox of ``crop_face`` without touching pixels: from 1.2 units above to 0.8 below the
+        nose and one unit either side of it, or None without a nose."""
         nx, ny, nv = person_pose[JointType.Nose][:3]
         if not nv > 0:
+            return None
+        return (int(nx - unit_length), int(ny - unit_length * 1.2), int(nx + unit_length), int(ny + unit_length * 0.8))
+
+    def crop_face(self, img, person_pose, unit_length):
+        """pose_detector.py:354-369: (face_img, bbox), or (None, None) without a nose."""
+        bbox = self.face_bbox(person_pose, unit_length)
+        if bbox is None:
             return None, None
-        bbox = (int(nx - unit_length), int(ny - unit_length * 1.2), int(nx + unit_length), int(ny + unit_length * 0.8))
         return self.crop_image(img, bbox), bbox
 
-    def crop_hands(self, img, person_pose, unit_length):
-        """pose_detector.py:371-399: {'left'|'right': {'img', 'bbox'} or None}; the centre moves 0.3 of
-        the elbow->hand vector past the hand.  Like the reference, that shift is written into
-        person_pose itself (the centre is a view of the hand row)."""
+    def hand_bboxes(self, person_pose, unit_length):
+        """The bboxes of ``crop_hands`` without touching pixels: {'left'|'right': bbox or None}; the
+        centre moves 0.3 of the elbow->hand vector past the hand.  Like the reference's crop_hands,
+        that shift is written into person_pose itself (the centre is a view of the hand row)."""
         out = {}
         for side, hand, elbow in (("left", JointType.LeftHand, JointType.LeftElbow),
                                   ("right", JointType.RightHand, JointType.RightElbow)):
@@ -229,9 +235,17 @@ class PoseDetector(object):
             centre = person_pose[hand][:-1]  # a view: the in-place shift below reaches person_pose
             if person_pose[elbow][2] > 0:
                 centre += (0.3 * (person_pose[hand][:-1] - person_pose[elbow][:-1])).astype(centre.dtype)
-            crop, bbox = self.crop_around_keypoint(img, centre, unit_length * 0.95)
-            out[side] = {"img": crop, "bbox": bbox}
+            x, y = centre
+            crop_size = unit_length * 0.95  # crop_around_keypoint's box
+            out[side] = tuple(int(v) for v in (x - crop_size, y - crop_size, x + crop_size, y + crop_size))
         return {"left": out["left"], "right": out["right"]}
+
+    def crop_hands(self, img, person_pose, unit_length):
+        """pose_detector.py:371-399: {'left'|'right': {'img', 'bbox'} or None} (hand_bboxes, with its
+        in-place shift of the hand rows, then crop_image)."""
+        boxes = self.hand_bboxes(person_pose, unit_length)
+        return {side: None if boxes[side] is None else {"img": self.crop_image(img, boxes[side]), "bbox": boxes[side]}
+                for side in ("left", "right")}
 
     def crop_image(self, img, bbox):
         """pose_detector.py:401-425: the (left, top, right, bottom) box of img; the parts of the box

@@ -472,6 +472,28 @@ int op_cpm_detect_batch(op_cpm_ctx* ctx, int32_t n, const uint8_t* const* bgr, c
 /* enable != 0: no split-K on small launches, so a crop's result does not depend on how many crops
  * share its batch (op_cpm_detect_batch == op_cpm_detect bit for bit).  Like op_set_batch_invariant. */
 int op_cpm_set_batch_invariant(op_cpm_ctx* ctx, int32_t enable);
+/* op_cpm_detect_batch fed from frames and boxes: ROI i is the box roi_box[4 i ..] = (l, t, r, b) of
+ * frame roi_frame[i] (bgr[f]: fh[f] x fw[f] x 3 u8, row stride row_stride[f]), read mirrored in x
+ * where roi_mirror[i] != 0 (may be NULL: none).  The crop is virtual: its (y, x) is
+ * frame[t + y][l + (mirror ? r-l-1-x : x)], 0 outside the frame (PoseDetector.crop_image, then
+ * [:, ::-1]); a mirrored ROI also reads its maps mirrored (the left hand of hand_detector.py).  Each
+ * frame is uploaded once, the tables (24 B per frame, 48 B per ROI) once, and the launches around the
+ * forward number 1 + 4 * groups whatever n is.  Results equal op_cpm_detect_batch on the host-made
+ * crops bit for bit: keypoints (n, c-1, 3) f64, found (n, c-1).  OP_ERR_INVALID (naming the frame or
+ * ROI) before anything is launched for: null pointers, n < 0, a frame index outside [0, n_frames), a
+ * frame below 1 x 1 or a row stride below 3 * w, r-l < 2 or b-t < 2, (r-l) * (b-t) >= 2^31, a
+ * coordinate beyond +-2^30.  n == 0: OP_OK, nothing is touched. */
+int op_cpm_detect_rois(op_cpm_ctx* ctx, int32_t n_frames, const uint8_t* const* bgr, const int32_t* fh,
+                       const int32_t* fw, const int64_t* row_stride, int32_t n, const int32_t* roi_frame,
+                       const int32_t* roi_box, const int32_t* roi_mirror, float thresh, double* keypoints,
+                       int32_t* found);
+/* Scratch budget of one post-process group of op_cpm_detect_rois (two f32 sets of the ROIs' full-size
+ * planes); consecutive ROIs share a group while they fit, a ROI beyond the budget alone is its own
+ * group.  0: the default (256 MiB). */
+int op_cpm_set_roi_group_bytes(op_cpm_ctx* ctx, int64_t bytes);
+/* The last successful op_cpm_detect_rois: out = {groups, launches outside the forward, bytes uploaded
+ * (packed frames + tables), scratch bytes laid out}. */
+int op_cpm_roi_stats(op_cpm_ctx* ctx, int64_t out[4]);
 
 /* ---- Training iteration: Updater.update_core of train_coco_pose_estimation.py:93-123 ----
  * One context = CocoPoseNet master weights (f32), Adam state and every activation of a batch of n
