@@ -42,6 +42,7 @@ EXPORTED = (
     "op_augment", "op_augment_last_ms", "op_augment_last_paths", "op_augment_tables",
     "op_ignore_masks", "op_ignore_masks_last_ms",
     "op_draw", "op_draw_staged", "op_staged_info", "op_draw_last_ms",
+    "op_overlay", "op_overlay_staged", "op_overlay_last_ms",
 )
 ARCH = {"facenet": 1, "handnet": 2}
 CPM_PROBE_HI = 256  # OP_CPM_PROBE_HI
@@ -198,6 +199,9 @@ def lib():
         "op_draw_staged": ([P, I32, I32, P, P, P], ctypes.c_int),
         "op_staged_info": ([P, P, P, P], ctypes.c_int),
         "op_draw_last_ms": ([I32, P], ctypes.c_int),
+        "op_overlay": ([I32, I32, P, P, P, P, P, P, P, P, P, P, P], ctypes.c_int),
+        "op_overlay_staged": ([P, I32, I32, I32, P, P], ctypes.c_int),
+        "op_overlay_last_ms": ([I32, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -109,10 +109,20 @@ def main(argv=None):
     ap.add_argument("--precise", action="store_true", help="do precise inference")
     ap.add_argument("--out", default="result.png", help="output image path")
     ap.add_argument("--device-draw", action="store_true", help="draw on the device (render.render), the same image")
+    ap.add_argument("--overlay", metavar="LAYERS", help="also write the frame with the network's maps over it: "
+                    "pafs, heatmaps or pafs,heatmaps (overlay.overlay_staged, on the device)")
+    ap.add_argument("--overlay-out", default="overlay.png", help="output path of --overlay")
     args = ap.parse_args(argv)
+    layers = set(args.overlay.split(",")) if args.overlay else set()
+    if args.overlay and (not layers or layers - {"pafs", "heatmaps"}):
+        ap.error("--overlay takes pafs, heatmaps or pafs,heatmaps")
     det = PoseDetector(args.arch, args.weights, device=args.gpu, precise=args.precise)
     img = read_bgr(args.img)
     poses, _ = det(img)
+    if layers:  # the frame and its maps are still on the device
+        from . import overlay
+        print("Saving the overlay into %s..." % args.overlay_out)
+        write_bgr(args.overlay_out, overlay.overlay_staged(det._ctx, 0, 1, "pafs" in layers, "heatmaps" in layers)[0])
     if args.device_draw:
         from . import render
         img = render.render([img], [render.pose_list(poses)], device=det.device)[0]

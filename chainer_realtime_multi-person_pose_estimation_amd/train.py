@@ -25,6 +25,10 @@ device produce the network-input frames and masks (op_augment) and hands them to
 ``Updater.update_annotated`` starts at the raw COCO annotations: the device makes each image's ignore
 mask from the segmentations first (masks.py, op_ignore_masks: gen_ignore_mask.py's ``gen_masks``).
 
+``--dump-samples DIR`` (``--data poses`` or ``samples``) writes the loader's viewer picture of the first
+``--dump-count`` training samples (coco_data_loader.py:372-384, ``dump_samples``): the frame beside the
+frame with its labels laid over it (overlay.py), without changing the training.
+
 ``Validator`` is the reference's (:129-159): every ``--val-interval`` iterations a fixed held-out set
 is scored with ``Updater.evaluate`` (op_train_eval: forward + compute_loss only, the training state
 is left alone) and ``val/loss``, ``val/paf``, ``val/heat`` join that log entry; at the same points
@@ -373,6 +377,27 @@ def validation_batches(seed, samples, valbatchsize, insize, data="maps", people=
     return out
 
 
+def dump_samples(out_dir, start, count, imgs, poses, mask, device=0):
+    """The reference viewer's picture (coco_data_loader.py:372-384) of up to ``count`` samples of a
+    batch as ``update_poses`` takes it, without the window: the labels made on the device
+    (labels.make_labels), laid over the frame on the device (overlay.overlay_labels), and
+    ``hstack(resized_img, overlay)`` written as sample_<index>.png, index from ``start``.  Returns the
+    number written."""
+    from . import overlay as _overlay
+    from .draw import write_bgr
+    k = min(int(count), len(imgs))
+    if k < 1:
+        return 0
+    imgs = [np.ascontiguousarray(a, np.uint8) for a in imgs[:k]]
+    h, w = imgs[0].shape[:2]
+    pafs, heat, ign = _labels.make_labels(poses[:k], h, w, None if mask is None else np.asarray(mask)[:k], device=device)
+    shown = _overlay.overlay_labels(imgs, pafs, heat, ign, device=device)
+    os.makedirs(out_dir, exist_ok=True)
+    for i in range(k):
+        write_bgr(os.path.join(out_dir, "sample_%04d.png" % (start + i)), np.hstack((imgs[i], shown[i])))
+    return k
+
+
 def _mean_entry(observations):
     """LogReport: one entry per interval, every key's mean over the iterations that reported it."""
     keys = []
@@ -409,7 +434,13 @@ def main(argv=None, ctx=None):
     ap.add_argument("--log-interval", type=int, default=1,
                     help="one log entry per this many iterations, holding the means over them")
     ap.add_argument("--test", action="store_true", help="validation interval 10, log interval 1")
+    ap.add_argument("--dump-samples", metavar="DIR", help="write hstack(frame, labels laid over it) PNGs of the "
+                    "first training samples (--data poses, samples): the reference loader's viewer")
+    ap.add_argument("--dump-count", type=int, default=8, help="how many samples --dump-samples writes")
     args = ap.parse_args(argv)
+    if args.dump_samples and args.data == "maps":
+        ap.error("--dump-samples shows labels made from keypoints: --data poses or samples")
+    to_dump = max(args.dump_count, 0) if args.dump_samples else 0  # samples still to be written
     if args.test:
         args.val_interval, args.log_interval = 10, 1
     if args.val_interval < 1 or args.log_interval < 1 or args.valbatchsize < 1 or args.val_samples < 1:
@@ -437,6 +468,8 @@ def main(argv=None, ctx=None):
             imgs = rng.integers(0, 256, (args.batchsize, args.insize, args.insize, 3), dtype=np.uint8)
             poses = synthetic_poses(rng, args.batchsize, args.insize, args.insize, args.people)
             mask = rng.random((args.batchsize, args.insize, args.insize)) < 0.0005
+            if to_dump:
+                to_dump -= dump_samples(args.dump_samples, args.dump_count - to_dump, to_dump, imgs, poses, mask, up.device)
             t0 = time.perf_counter()
             loss, pl, hl = up.update_poses(imgs, poses, mask)
             dt = time.perf_counter() - t0
@@ -446,9 +479,16 @@ def main(argv=None, ctx=None):
         elif args.data == "samples":
             samples = synthetic_samples(rng, args.batchsize, args.people)
             t0 = time.perf_counter()
-            loss, pl, hl = up.update_samples(samples, py_random, np_random)
+            if to_dump:  # update_samples' two steps, with the augmented batch shown in between
+                batch = _augment.augment_batch(samples, args.insize, py_random, np_random, up.device)
+                augment_ms = _augment.last_ms(up.device)
+                to_dump -= dump_samples(args.dump_samples, args.dump_count - to_dump, to_dump, *batch, device=up.device)
+                loss, pl, hl = up.update_poses(*batch)
+            else:
+                loss, pl, hl = up.update_samples(samples, py_random, np_random)
+                augment_ms = _augment.last_ms(up.device)
             dt = time.perf_counter() - t0
-            augment_ms, label_ms = _augment.last_ms(up.device), up.ctx.last_label_ms()
+            label_ms = up.ctx.last_label_ms()
             extra = {"augment_ms": augment_ms, "label_ms": label_ms}
             note = ", augment %.3f ms, labels %.3f ms" % (augment_ms, label_ms)
         else:

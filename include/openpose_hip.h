@@ -717,6 +717,45 @@ int op_staged_info(op_ctx* ctx, int32_t* n, int32_t* h, int32_t* w);
  * op_draw_staged that completed on `device`; OP_ERR_STATE before the first. */
 int op_draw_last_ms(int32_t device, double* ms);
 
+/* ---- PAFs, heat maps and the ignore mask over frames (overlay.py; coco_data_loader.py:29-59, 372-382) ----
+ * A batch of n frames of any sizes on `device`: bgr[f] is frame f's hw[2f] x hw[2f + 1] (h, w) x 3 u8
+ * image with row_stride[f] bytes per row, out[f] a host pointer to h * w * 3 u8.  Each of pafs, heat
+ * and mask may be NULL as a whole or hold a NULL entry for one frame: no such layer there.  pafs[f] is
+ * f32 (2L, mh, mw) with paf_chw[3f ..] = (2L, mh, mw), heat[f] f32 (C, mh, mw) with heat_chw[3f ..] =
+ * (C, mh, mw), mask[f] u8 (h, w) of any size with mask_hw[2f ..] = (h, w), nonzero = ignored; lut is
+ * the 256 x 3 u8 BGR colour table of the heat layer, required when any frame has one.  Per pixel, in
+ * this order: the maps resampled to the frame (cv2.resize INTER_LINEAR on f32, one rounded f32
+ * operation each; equal sizes are copied), the limbs of the PAFs summed in f64 and shown as hue =
+ * direction, saturation = value = magnitude, blended 0.6 / 0.4; the f32 maximum over the heat
+ * channels * 255, clamped to 0 .. 255 and truncated, through lut, blended alike; the pixel set to 0
+ * where cv2.resize(mask * 255) > 0.  One kernel launch for the whole batch, one workgroup per 64 x 16
+ * pixel tile of a frame; the result is overlay.py's overlay_np bit for bit, given that the f64 atan2
+ * lands in the same of the 256 hue levels (overlay.hue_margin).  The colour table, the f32 resize and
+ * HSV2BGR restate OpenCV and stay unpinned against it.
+ * Arguments are validated before any device call (OP_ERR_INVALID, the message names the field): n < 1,
+ * null arrays or entries that are required, h or w outside 1 .. 16384, a row stride below 3 w, a PAF
+ * channel count that is odd or not positive, a heat channel count below 1, a map or mask side outside
+ * 1 .. 16384.  Maps that are not finite are not refused here (overlay.py refuses them): the call is
+ * safe, every table index is clamped by comparisons that are false for NaN, and the pixels such
+ * values reach are unspecified. */
+int op_overlay(int32_t device, int32_t n, const uint8_t* const* bgr, const int64_t* row_stride, const int32_t* hw,
+               const float* const* pafs, const int32_t* paf_chw, const float* const* heat, const int32_t* heat_chw,
+               const uint8_t* const* mask, const int32_t* mask_hw, const uint8_t* lut, uint8_t* const* out);
+/* The same kernel on staged frames [first, first + n) of ctx and on the maps op_fetch_maps would
+ * return for them, all read in place on the device: after op_run_staged* the last-stage network maps,
+ * after op_run_staged_precise the averaged full-resolution maps (copied through, not resampled).
+ * layers is a bit set; the heat layer shows channels 0 .. 17 (the background channel is left out, as
+ * in the reference) and needs lut.  out is n * h * w * 3 u8 on the host.  The kernel runs on the
+ * context stream, behind a queued op_run_staged*; the call returns when out is filled.  Staged
+ * frames, maps and results are not modified.  OP_ERR_STATE when nothing is staged or no run has
+ * produced maps of the staged frames, OP_ERR_INVALID for a range outside the staged set. */
+#define OP_OVERLAY_PAFS 1
+#define OP_OVERLAY_HEAT 2
+int op_overlay_staged(op_ctx* ctx, int32_t first, int32_t n, int32_t layers, const uint8_t* lut, uint8_t* out);
+/* Device time (ms, stream events) of the uploads and the kernel of the last op_overlay or
+ * op_overlay_staged that completed on `device`; OP_ERR_STATE before the first. */
+int op_overlay_last_ms(int32_t device, double* ms);
+
 #ifdef __cplusplus
 }
 #endif
