@@ -41,6 +41,7 @@ EXPORTED = (
     "op_train_buffer_info", "op_train_read_buffer",
     "op_augment", "op_augment_last_ms", "op_augment_last_paths", "op_augment_tables",
     "op_ignore_masks", "op_ignore_masks_last_ms",
+    "op_annotation_views", "op_annotation_views_last_ms",
     "op_draw", "op_draw_staged", "op_staged_info", "op_draw_last_ms",
     "op_overlay", "op_overlay_staged", "op_overlay_last_ms",
 )
@@ -195,6 +196,8 @@ def lib():
         "op_augment_tables": ([P, P, P, P], ctypes.c_int),
         "op_ignore_masks": ([I32, I32, P, P, P, P, P, P, P, P, P, P, P], ctypes.c_int),
         "op_ignore_masks_last_ms": ([I32, P], ctypes.c_int),
+        "op_annotation_views": ([I32, I32, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P], ctypes.c_int),
+        "op_annotation_views_last_ms": ([I32, P], ctypes.c_int),
         "op_draw": ([I32, I32, P, P, P, P, P, P], ctypes.c_int),
         "op_draw_staged": ([P, I32, I32, P, P, P], ctypes.c_int),
         "op_staged_info": ([P, P, P, P], ctypes.c_int),
@@ -1203,3 +1206,27 @@ def ignore_masks_call(device, n, packed, out_all=None, out_miss=None, out_ann=No
     check(lib().op_ignore_masks(int(device), int(n), ptr(packed["hw"]), ptr(packed["ann_offsets"]), arr("ann_role"),
                                 ptr(packed["part_offsets"]), arr("part_kind"), ptr(packed["data_offsets"]),
                                 arr("xy"), arr("counts"), *tabs), "op_ignore_masks")
+
+
+def annotation_views_call(device, frames, packed, out_ann=None, out_miss=None):
+    """op_annotation_views on ``maskview.pack_views``' arrays: frames are (h, w, 3) uint8 arrays whose
+    pixels are packed within a row (packed["row_stride"] bytes per row); out_* are lists of
+    C-contiguous (h, w, 3) u8 arrays (or None entries, or None) that the call fills."""
+    def table(arrays):
+        if arrays is None:
+            return None
+        for a in arrays:
+            if a is not None and not (a.dtype == np.uint8 and a.flags.c_contiguous):
+                raise ValueError("op_annotation_views: outputs are C-contiguous uint8 arrays")
+        return (ctypes.c_void_p * max(len(arrays), 1))(*[a.ctypes.data if a is not None else None for a in arrays])
+
+    def arr(name):
+        return ptr(packed[name]) if packed[name].size else None
+
+    n = len(frames)
+    bgr = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data for a in frames])
+    check(lib().op_annotation_views(int(device), n, bgr, ptr(packed["row_stride"]), ptr(packed["hw"]),
+                                    ptr(packed["ann_offsets"]), arr("ann_role"), arr("ann_tint"),
+                                    ptr(packed["part_offsets"]), arr("part_kind"), ptr(packed["data_offsets"]),
+                                    arr("xy"), arr("counts"), ptr(packed["kp_offsets"]), arr("kp"),
+                                    table(out_ann), table(out_miss)), "op_annotation_views")

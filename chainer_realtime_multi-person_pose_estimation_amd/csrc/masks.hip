@@ -23,6 +23,8 @@
 //     threads, and the column bits before the block as the carry-in.  The parts of an annotation
 //     are ORed, mask_all / mask_miss of the block are kept in LDS under the three role rules, and
 //     the row-major u8 masks are written at the end (an annotation's own mask only when asked for).
+// mask_pack and mask_launch (masks.hpp) are shared with maskview.hip, whose kernel reads the masks
+// where mask_fill left them.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -33,6 +35,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "masks.hpp"
 
 namespace op {
 namespace {
@@ -45,30 +48,6 @@ constexpr int kFillThreads = 256;
 constexpr int kFillWords = 2048;  // LDS words per bit array of a column block
 constexpr int kFillMaxCols = 64;
 
-struct MaskImage {
-  int64_t out_off;  // into the mask_all / mask_miss buffers
-  int32_t h, w, ann0, ann1;
-};
-struct MaskAnn {
-  int64_t out_off;  // into the per-annotation buffer; < 0: not wanted
-  int32_t role, part0, part1, pad;
-};
-struct MaskPart {
-  int64_t plane_off;  // words; the column bits follow the tw toggle words
-  int32_t tw, pad;
-};
-struct MaskEdge {
-  double s;
-  int64_t plane_off;
-  int32_t xs, ys, len, major, flip, h, w, tw;  // len = max(dx, dy): the points 1 .. len
-};
-struct MaskRle {
-  int64_t plane_off, data_off;
-  int32_t n, h, tw, pad;
-};
-struct MaskBlock {
-  int32_t image, c0, nc, pad;
-};
 struct MaskArgs {
   const MaskImage* images;
   const MaskAnn* anns;
@@ -245,60 +224,50 @@ __global__ __launch_bounds__(kFillThreads) void mask_fill(MaskArgs a) {
 }
 
 // ---- host ----
-int mask_invalid(const std::string& msg) {
-  set_error("op_ignore_masks: " + msg);
+int mask_invalid(const char* who, const std::string& msg) {
+  set_error(std::string(who) + ": " + msg);
   return OP_ERR_INVALID;
 }
 
-struct MaskHost {
-  std::vector<MaskImage> images;
-  std::vector<MaskAnn> anns;
-  std::vector<MaskPart> parts;
-  std::vector<MaskEdge> edges;
-  std::vector<int32_t> edge_start;
-  std::vector<MaskRle> rles;
-  std::vector<uint32_t> counts;
-  std::vector<MaskBlock> blocks;
-  int64_t plane_words = 0, out_bytes = 0, ann_bytes = 0;
-};
-
 int64_t pad16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
-int mask_offsets(const char* name, const int64_t* o64, const int32_t* o32, int64_t count) {
-  if (!o64 && !o32) return mask_invalid(std::string("null ") + name);
+}  // namespace
+
+int mask_offsets(const char* who, const char* name, const int64_t* o64, const int32_t* o32, int64_t count) {
+  if (!o64 && !o32) return mask_invalid(who, std::string("null ") + name);
   int64_t prev = 0;
   for (int64_t i = 0; i <= count; ++i) {
     const int64_t v = o64 ? o64[i] : (int64_t)o32[i];
     if ((i == 0 && v != 0) || v < prev)
-      return mask_invalid(std::string(name) + ": entry " + std::to_string(i) + " must start at 0 and never decrease");
+      return mask_invalid(who, std::string(name) + ": entry " + std::to_string(i) + " must start at 0 and never decrease");
     prev = v;
   }
   return OP_OK;
 }
 
-int mask_pack(int32_t n, const int32_t* hw, const int32_t* ann_offsets, const int32_t* ann_role,
+int mask_pack(const char* who, int32_t n, const int32_t* hw, const int32_t* ann_offsets, const int32_t* ann_role,
               const int32_t* part_offsets, const int32_t* part_kind, const int64_t* data_offsets, const double* xy,
-              const uint32_t* counts, uint8_t* const* out_ann, MaskHost* out) {
-  if (n < 1 || n > (1 << 20)) return mask_invalid("n must be in 1 .. 1048576");
-  if (!hw) return mask_invalid("null hw");
+              const uint32_t* counts, uint8_t* const* out_ann, uint8_t* const* ann_frames, MaskHost* out) {
+  if (n < 1 || n > (1 << 20)) return mask_invalid(who, "n must be in 1 .. 1048576");
+  if (!hw) return mask_invalid(who, "null hw");
   for (int f = 0; f < n; ++f)
     if (hw[2 * f] < 1 || hw[2 * f] > kMaskMaxSide || hw[2 * f + 1] < 1 || hw[2 * f + 1] > kMaskMaxSide)
-      return mask_invalid("hw: image " + std::to_string(f) + ": h, w must be in 1 .. 16384");
-  int rc = mask_offsets("ann_offsets", nullptr, ann_offsets, n);
+      return mask_invalid(who, "hw: image " + std::to_string(f) + ": h, w must be in 1 .. 16384");
+  int rc = mask_offsets(who, "ann_offsets", nullptr, ann_offsets, n);
   if (rc) return rc;
   const int32_t A = ann_offsets[n];
-  if (A > 0 && !ann_role) return mask_invalid("null ann_role");
+  if (A > 0 && !ann_role) return mask_invalid(who, "null ann_role");
   for (int a = 0; a < A; ++a)
     if (ann_role[a] != OP_MASK_KEEP && ann_role[a] != OP_MASK_MISS && ann_role[a] != OP_MASK_CROWD)
-      return mask_invalid("ann_role: annotation " + std::to_string(a) + ": unknown role " + std::to_string(ann_role[a]));
-  rc = mask_offsets("part_offsets", nullptr, part_offsets, A);
+      return mask_invalid(who, "ann_role: annotation " + std::to_string(a) + ": unknown role " + std::to_string(ann_role[a]));
+  rc = mask_offsets(who, "part_offsets", nullptr, part_offsets, A);
   if (rc) return rc;
   const int32_t P = part_offsets[A];
-  if (P > 0 && !part_kind) return mask_invalid("null part_kind");
+  if (P > 0 && !part_kind) return mask_invalid(who, "null part_kind");
   for (int p = 0; p < P; ++p)
     if (part_kind[p] != OP_MASK_POLYGON && part_kind[p] != OP_MASK_RLE)
-      return mask_invalid("part_kind: part " + std::to_string(p) + ": unknown kind " + std::to_string(part_kind[p]));
-  rc = mask_offsets("data_offsets", data_offsets, nullptr, P);
+      return mask_invalid(who, "part_kind: part " + std::to_string(p) + ": unknown kind " + std::to_string(part_kind[p]));
+  rc = mask_offsets(who, "data_offsets", data_offsets, nullptr, P);
   if (rc) return rc;
   int64_t points = 0;
   for (int f = 0; f < n; ++f) {
@@ -307,18 +276,18 @@ int mask_pack(int32_t n, const int32_t* hw, const int32_t* ann_offsets, const in
       const int64_t lo = data_offsets[p], len = data_offsets[p + 1] - lo;
       const std::string at = "part " + std::to_string(p) + ": ";
       if (part_kind[p] == OP_MASK_POLYGON) {
-        if (!xy) return mask_invalid("null xy");
+        if (!xy) return mask_invalid(who, "null xy");
         if (len % 2 || len < 6)
-          return mask_invalid("xy: " + at + "a polygon of " + std::to_string(len) + " numbers (an even count, at least 3 points)");
+          return mask_invalid(who, "xy: " + at + "a polygon of " + std::to_string(len) + " numbers (an even count, at least 3 points)");
         for (int64_t i = 0; i < len; ++i)
           if (!std::isfinite(xy[lo + i]) || std::fabs(xy[lo + i]) > kMaskMaxCoord)
-            return mask_invalid("xy: " + at + "a coordinate that is not finite or above 65536 in magnitude");
+            return mask_invalid(who, "xy: " + at + "a coordinate that is not finite or above 65536 in magnitude");
       } else {
-        if (!counts) return mask_invalid("null counts");
+        if (!counts) return mask_invalid(who, "null counts");
         uint64_t sum = 0;
         for (int64_t i = 0; i < len; ++i) sum += counts[lo + i];
         if (sum != (uint64_t)pixels)
-          return mask_invalid("counts: " + at + "the runs sum to " + std::to_string(sum) + ", the image has " +
+          return mask_invalid(who, "counts: " + at + "the runs sum to " + std::to_string(sum) + ", the image has " +
                               std::to_string(pixels) + " pixels");
       }
     }
@@ -344,7 +313,7 @@ int mask_pack(int32_t n, const int32_t* hw, const int32_t* ann_offsets, const in
       an.part1 = part_offsets[a + 1];
       an.pad = 0;
       an.out_off = -1;
-      if (out_ann && out_ann[a]) {
+      if ((out_ann && out_ann[a]) || (ann_frames && ann_frames[f])) {
         an.out_off = out->ann_bytes;
         out->ann_bytes += pad16((int64_t)im.h * im.w);
       }
@@ -363,7 +332,7 @@ int mask_pack(int32_t n, const int32_t* hw, const int32_t* ann_offsets, const in
           r.h = im.h;
           r.tw = tw;
           r.pad = 0;
-          if (len > INT32_MAX) return mask_invalid("counts: part " + std::to_string(p) + ": too many runs");
+          if (len > INT32_MAX) return mask_invalid(who, "counts: part " + std::to_string(p) + ": too many runs");
           out->counts.insert(out->counts.end(), counts + lo, counts + lo + len);
           out->rles.push_back(r);
           continue;
@@ -396,7 +365,7 @@ int mask_pack(int32_t n, const int32_t* hw, const int32_t* ann_offsets, const in
           e.w = im.w;
           e.tw = tw;
           points += e.len;
-          if (points > INT32_MAX) return mask_invalid("xy: more than 2^31 - 1 upsampled outline points in the batch");
+          if (points > INT32_MAX) return mask_invalid(who, "xy: more than 2^31 - 1 upsampled outline points in the batch");
           out->edges.push_back(e);
           out->edge_start.push_back((int32_t)points);
         }
@@ -409,10 +378,70 @@ int mask_pack(int32_t n, const int32_t* hw, const int32_t* ann_offsets, const in
   return OP_OK;
 }
 
+MaskDevice::~MaskDevice() {
+  for (void* p : d)
+    if (p) (void)hipFree(p);
+}
+
+hipError_t mask_launch(const MaskHost& mh, MaskDevice* md, hipEvent_t start, const char** what) {
+  enum { IMAGES = MaskDevice::IMAGES, ANNS = MaskDevice::ANNS, PARTS = MaskDevice::PARTS, EDGES = MaskDevice::EDGES,
+         ESTART = MaskDevice::ESTART, RLES = MaskDevice::RLES, COUNTS = MaskDevice::COUNTS, BLOCKS = MaskDevice::BLOCKS,
+         PLANES = MaskDevice::PLANES, OALL = MaskDevice::OALL, OMISS = MaskDevice::OMISS, OANN = MaskDevice::OANN,
+         NBUF = MaskDevice::NBUF };
+  const void* host[NBUF] = {mh.images.data(), mh.anns.data(), mh.parts.data(), mh.edges.data(), mh.edge_start.data(),
+                            mh.rles.data(), mh.counts.data(), mh.blocks.data(), nullptr, nullptr, nullptr, nullptr};
+  const size_t sizes[NBUF] = {mh.images.size() * sizeof(MaskImage), mh.anns.size() * sizeof(MaskAnn),
+                              mh.parts.size() * sizeof(MaskPart), mh.edges.size() * sizeof(MaskEdge),
+                              mh.edge_start.size() * sizeof(int32_t), mh.rles.size() * sizeof(MaskRle),
+                              mh.counts.size() * sizeof(uint32_t), mh.blocks.size() * sizeof(MaskBlock),
+                              (size_t)mh.plane_words * sizeof(uint32_t), (size_t)mh.out_bytes, (size_t)mh.out_bytes,
+                              (size_t)mh.ann_bytes};
+  void** d = md->d;
+  hipError_t e = hipSuccess;
+  *what = "hipMalloc";
+  for (int i = 0; i < NBUF; ++i)
+    if (sizes[i] && (e = hipMalloc(&d[i], sizes[i])) != hipSuccess) return e;
+  *what = "hipEventRecord";
+  if (start && (e = hipEventRecord(start, nullptr)) != hipSuccess) return e;
+  *what = "upload";
+  for (int i = 0; i < NBUF; ++i)
+    if (host[i] && sizes[i] && (e = hipMemcpy(d[i], host[i], sizes[i], hipMemcpyHostToDevice)) != hipSuccess) return e;
+  *what = "hipMemset";
+  if (sizes[PLANES] && (e = hipMemset(d[PLANES], 0, sizes[PLANES])) != hipSuccess) return e;
+  MaskArgs a;
+  a.images = (const MaskImage*)d[IMAGES];
+  a.anns = (const MaskAnn*)d[ANNS];
+  a.parts = (const MaskPart*)d[PARTS];
+  a.edges = (const MaskEdge*)d[EDGES];
+  a.edge_start = (const int32_t*)d[ESTART];
+  a.rles = (const MaskRle*)d[RLES];
+  a.counts = (const uint32_t*)d[COUNTS];
+  a.blocks = (const MaskBlock*)d[BLOCKS];
+  a.planes = (uint32_t*)d[PLANES];
+  a.out_all = (uint8_t*)d[OALL];
+  a.out_miss = (uint8_t*)d[OMISS];
+  a.out_ann = (uint8_t*)d[OANN];
+  a.n_edges = (int32_t)mh.edges.size();
+  a.total_points = mh.edge_start.back();
+  if (a.total_points > 0) {
+    *what = "mask_toggles";
+    hipLaunchKernelGGL(mask_toggles, dim3((unsigned)(((int64_t)a.total_points + 255) / 256)), dim3(256), 0, nullptr, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  if (!mh.rles.empty()) {
+    *what = "mask_rle";
+    hipLaunchKernelGGL(mask_rle, dim3((unsigned)mh.rles.size()), dim3(256), 0, nullptr, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  *what = "mask_fill";
+  hipLaunchKernelGGL(mask_fill, dim3((unsigned)mh.blocks.size()), dim3(kFillThreads), 0, nullptr, a);
+  return hipGetLastError();
+}
+
+namespace {
 std::mutex g_mask_mutex;
 double g_mask_ms[kMaskMaxDevices];
 bool g_mask_ran[kMaskMaxDevices];
-
 }  // namespace
 }  // namespace op
 
@@ -423,7 +452,8 @@ extern "C" int op_ignore_masks(int32_t device, int32_t n, const int32_t* hw, con
                                const int64_t* data_offsets, const double* xy, const uint32_t* counts,
                                uint8_t* const* out_all, uint8_t* const* out_miss, uint8_t* const* out_ann) {
   MaskHost mh;
-  const int rc = mask_pack(n, hw, ann_offsets, ann_role, part_offsets, part_kind, data_offsets, xy, counts, out_ann, &mh);
+  const int rc = mask_pack("op_ignore_masks", n, hw, ann_offsets, ann_role, part_offsets, part_kind, data_offsets, xy,
+                           counts, out_ann, nullptr, &mh);
   if (rc) return rc;
   int ndev = 0;
   OP_HIP_CHECK(hipGetDeviceCount(&ndev));
@@ -432,16 +462,7 @@ extern "C" int op_ignore_masks(int32_t device, int32_t n, const int32_t* hw, con
     return OP_ERR_INVALID;
   }
   OP_HIP_CHECK(hipSetDevice(device));
-  enum { IMAGES, ANNS, PARTS, EDGES, ESTART, RLES, COUNTS, BLOCKS, PLANES, OALL, OMISS, OANN, NBUF };
-  const void* host[NBUF] = {mh.images.data(), mh.anns.data(), mh.parts.data(), mh.edges.data(), mh.edge_start.data(),
-                            mh.rles.data(), mh.counts.data(), mh.blocks.data(), nullptr, nullptr, nullptr, nullptr};
-  const size_t sizes[NBUF] = {mh.images.size() * sizeof(MaskImage), mh.anns.size() * sizeof(MaskAnn),
-                              mh.parts.size() * sizeof(MaskPart), mh.edges.size() * sizeof(MaskEdge),
-                              mh.edge_start.size() * sizeof(int32_t), mh.rles.size() * sizeof(MaskRle),
-                              mh.counts.size() * sizeof(uint32_t), mh.blocks.size() * sizeof(MaskBlock),
-                              (size_t)mh.plane_words * sizeof(uint32_t), (size_t)mh.out_bytes, (size_t)mh.out_bytes,
-                              (size_t)mh.ann_bytes};
-  void* d[NBUF] = {};
+  MaskDevice md;
   hipEvent_t ev[2] = {};
   int res = OP_OK;
   auto fail = [&](hipError_t e, const char* what) {
@@ -449,41 +470,11 @@ extern "C" int op_ignore_masks(int32_t device, int32_t n, const int32_t* hw, con
     set_error(std::string("op_ignore_masks: ") + what + ": " + hipGetErrorString(e));
     res = OP_ERR_HIP;
   };
-  for (int i = 0; i < NBUF && !res; ++i)
-    if (sizes[i]) fail(hipMalloc(&d[i], sizes[i]), "hipMalloc");
   for (int i = 0; i < 2 && !res; ++i) fail(hipEventCreate(&ev[i]), "hipEventCreate");
-  if (!res) fail(hipEventRecord(ev[0], nullptr), "hipEventRecord");
-  for (int i = 0; i < NBUF && !res; ++i)
-    if (host[i] && sizes[i]) fail(hipMemcpy(d[i], host[i], sizes[i], hipMemcpyHostToDevice), "upload");
-  if (!res && sizes[PLANES]) fail(hipMemset(d[PLANES], 0, sizes[PLANES]), "hipMemset");
   if (!res) {
-    MaskArgs a;
-    a.images = (const MaskImage*)d[IMAGES];
-    a.anns = (const MaskAnn*)d[ANNS];
-    a.parts = (const MaskPart*)d[PARTS];
-    a.edges = (const MaskEdge*)d[EDGES];
-    a.edge_start = (const int32_t*)d[ESTART];
-    a.rles = (const MaskRle*)d[RLES];
-    a.counts = (const uint32_t*)d[COUNTS];
-    a.blocks = (const MaskBlock*)d[BLOCKS];
-    a.planes = (uint32_t*)d[PLANES];
-    a.out_all = (uint8_t*)d[OALL];
-    a.out_miss = (uint8_t*)d[OMISS];
-    a.out_ann = (uint8_t*)d[OANN];
-    a.n_edges = (int32_t)mh.edges.size();
-    a.total_points = mh.edge_start.back();
-    if (a.total_points > 0) {
-      hipLaunchKernelGGL(mask_toggles, dim3((unsigned)(((int64_t)a.total_points + 255) / 256)), dim3(256), 0, nullptr, a);
-      fail(hipGetLastError(), "mask_toggles");
-    }
-    if (!res && !mh.rles.empty()) {
-      hipLaunchKernelGGL(mask_rle, dim3((unsigned)mh.rles.size()), dim3(256), 0, nullptr, a);
-      fail(hipGetLastError(), "mask_rle");
-    }
-    if (!res) {
-      hipLaunchKernelGGL(mask_fill, dim3((unsigned)mh.blocks.size()), dim3(kFillThreads), 0, nullptr, a);
-      fail(hipGetLastError(), "mask_fill");
-    }
+    const char* what = "";
+    const hipError_t e = mask_launch(mh, &md, ev[0], &what);
+    fail(e, what);
   }
   if (!res) fail(hipEventRecord(ev[1], nullptr), "hipEventRecord");
   if (!res) fail(hipDeviceSynchronize(), "kernels");
@@ -493,16 +484,14 @@ extern "C" int op_ignore_masks(int32_t device, int32_t n, const int32_t* hw, con
     const MaskImage& im = mh.images[f];
     const size_t bytes = (size_t)im.h * im.w;
     if (out_all && out_all[f])
-      fail(hipMemcpy(out_all[f], (uint8_t*)d[OALL] + im.out_off, bytes, hipMemcpyDeviceToHost), "mask_all download");
+      fail(hipMemcpy(out_all[f], md.all() + im.out_off, bytes, hipMemcpyDeviceToHost), "mask_all download");
     if (out_miss && out_miss[f])
-      fail(hipMemcpy(out_miss[f], (uint8_t*)d[OMISS] + im.out_off, bytes, hipMemcpyDeviceToHost), "mask_miss download");
+      fail(hipMemcpy(out_miss[f], md.miss() + im.out_off, bytes, hipMemcpyDeviceToHost), "mask_miss download");
     for (int a = im.ann0; a < im.ann1 && !res; ++a)
       if (mh.anns[a].out_off >= 0)
-        fail(hipMemcpy(out_ann[a], (uint8_t*)d[OANN] + mh.anns[a].out_off, bytes, hipMemcpyDeviceToHost),
+        fail(hipMemcpy(out_ann[a], md.ann() + mh.anns[a].out_off, bytes, hipMemcpyDeviceToHost),
              "annotation mask download");
   }
-  for (void* p : d)
-    if (p) (void)hipFree(p);
   for (hipEvent_t e : ev)
     if (e) (void)hipEventDestroy(e);
   if (!res) {

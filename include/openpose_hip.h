@@ -666,6 +666,40 @@ int op_ignore_masks(int32_t device, int32_t n, const int32_t* hw, const int32_t*
  * completed on `device`; OP_ERR_STATE before the first. */
 int op_ignore_masks_last_ms(int32_t device, double* ms);
 
+/* ---- The --vis viewer of gen_ignore_mask.py (:39-71 draw_masks_and_keypoints, dwaw_gen_masks) ----
+ * A batch of n frames of any sizes on `device`.  bgr[f] is frame f's hw[2f] x hw[2f + 1] (h, w) x 3 u8
+ * image with row_stride[f] bytes per row (host pointers, as for op_draw).  hw, ann_offsets, ann_role,
+ * part_offsets, part_kind, data_offsets, xy and counts are op_ignore_masks' arguments, unchanged.
+ * ann_tint[a] is the colour annotation a's mask is tinted with, decided by the caller as ann_role is:
+ * the code is the BGR channel the tint raises (OP_VIEW_PERSON (1, 0, 0), OP_VIEW_NO_KEYPOINTS (0, 1, 0),
+ * OP_VIEW_CROWD (0, 0, 1) in the reference's tuples).  Annotation a owns the keypoints
+ * kp_offsets[a] .. kp_offsets[a + 1] - 1 of kp, int32 (x, y, v) triples: v = 1 paints a filled
+ * radius-3 disc (255, 255, 0), v = 2 one of (255, 0, 255), any other v nothing (draw.draw_disc's pixels:
+ * dx * dx + dy * dy <= 9).
+ * out_ann[f]: host pointer to h * w * 3 u8, draw_masks_and_keypoints(frame, annotations): a float64
+ * image carried from annotation to annotation, per annotation in order v = (v + 0.7 * c * 255) - 0.7 * v
+ * under its mask and then its discs in order, one truncating cast at the end.  out_miss[f]:
+ * dwaw_gen_masks(frame, mask_miss), that step once with (0, 0, 1) under gen_masks' mask_miss.  Either
+ * array, or any entry, may be null: not wanted.  The result is maskview.py's view_np byte for byte
+ * (the disc and polygon rasterisers stay unpinned against OpenCV's and pycocotools').
+ * The masks come from op_ignore_masks' three kernels and stay on the device; then one kernel launch
+ * for the whole batch, one workgroup per 64 x 16 pixel tile of a frame.
+ * Arguments are validated before any device call (OP_ERR_INVALID, the message names the field):
+ * everything op_ignore_masks refuses, null bgr / row_stride or a null frame, a row stride below 3 w, an
+ * unknown tint, kp_offsets that do not start at 0 or decrease, null kp with keypoints, a keypoint
+ * coordinate above 32768 in magnitude. */
+#define OP_VIEW_PERSON 0
+#define OP_VIEW_NO_KEYPOINTS 1
+#define OP_VIEW_CROWD 2
+int op_annotation_views(int32_t device, int32_t n, const uint8_t* const* bgr, const int64_t* row_stride,
+                        const int32_t* hw, const int32_t* ann_offsets, const int32_t* ann_role, const int32_t* ann_tint,
+                        const int32_t* part_offsets, const int32_t* part_kind, const int64_t* data_offsets,
+                        const double* xy, const uint32_t* counts, const int32_t* kp_offsets, const int32_t* kp,
+                        uint8_t* const* out_ann, uint8_t* const* out_miss);
+/* Device time (ms, stream events) of the uploads and kernels (the mask kernels and the view kernel)
+ * of the last op_annotation_views that completed on `device`; OP_ERR_STATE before the first. */
+int op_annotation_views_last_ms(int32_t device, double* ms);
+
 /* ---- Skeleton overlays from a display list (draw.py draw_line / draw_disc, demo.py add_weighted) ----
  * One primitive of a frame's display list (render.py builds the lists on the host).  A frame's
  * primitives are painted in order, a later one over an earlier one:
