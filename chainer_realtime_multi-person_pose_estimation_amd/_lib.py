@@ -44,6 +44,8 @@ EXPORTED = (
     "op_annotation_views", "op_annotation_views_last_ms",
     "op_draw", "op_draw_staged", "op_staged_info", "op_draw_last_ms",
     "op_overlay", "op_overlay_staged", "op_overlay_last_ms",
+    "op_cpm_detect_rois_staged", "op_cpm_set_roi_batch",
+    "op_body_rois", "op_body_rois_staged", "op_body_last_ms",
 )
 ARCH = {"facenet": 1, "handnet": 2}
 CPM_PROBE_HI = 256  # OP_CPM_PROBE_HI
@@ -205,6 +207,11 @@ def lib():
         "op_overlay": ([I32, I32, P, P, P, P, P, P, P, P, P, P, P], ctypes.c_int),
         "op_overlay_staged": ([P, I32, I32, I32, P, P], ctypes.c_int),
         "op_overlay_last_ms": ([I32, P], ctypes.c_int),
+        "op_cpm_detect_rois_staged": ([P, P, I32, I32, I32, P, P, P, ctypes.c_float, P, P], ctypes.c_int),
+        "op_cpm_set_roi_batch": ([P, I32], ctypes.c_int),
+        "op_body_rois": ([I32, I32, P, P, P, P], ctypes.c_int),
+        "op_body_rois_staged": ([P, I32, I32, I32, P, P, P, P, P], ctypes.c_int),
+        "op_body_last_ms": ([I32, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -704,6 +711,25 @@ class Context(object):
             break
         return [(poses[i, :res[i].n_persons].copy(), scores[i, :res[i].n_persons].copy(), res[i]) for i in range(n)]
 
+    def body_rois(self, first, n, cap=64):
+        """Face / hand boxes of the persons of staged frames [first, first + n), made on the device
+        from the result rows where they lie (op_body_rois_staged; wholebody.body_rois_np states them):
+        -> (count (n,), frame_status (n,), unit (n, cap), box (n, cap, 3, 4), state (n, cap, 3)); the
+        persons of frame i are rows [:min(count[i], cap)].  A frame with more persons than ``cap`` raises
+        nothing here: its ``count`` says so and the caller takes it through ``fetch_result`` and
+        ``_lib.body_rois`` (as it does a frame whose ``frame_status`` is OP_ERR_CAPACITY)."""
+        n, cap = int(n), int(cap)
+        count = np.zeros(max(n, 1), np.int32)
+        status = np.zeros(max(n, 1), np.int32)
+        unit = np.zeros((max(n, 1), max(cap, 1)), np.float64)
+        box = np.zeros((max(n, 1), max(cap, 1), 3, 4), np.int32)
+        state = np.zeros((max(n, 1), max(cap, 1), 3), np.int32)
+        rc = lib().op_body_rois_staged(self.h, int(first), n, cap, ptr(count), ptr(status), ptr(unit), ptr(box),
+                                       ptr(state))
+        if not (rc == OP_ERR_CAPACITY and count.max() > cap):
+            check(rc, "op_body_rois_staged")
+        return count, status, unit, box, state
+
     def fetch_maps(self, first=0, n=1):
         """Network maps of staged frames [first, first+n): (pafs (n,38,h,w), heatmaps (n,19,h,w)) --
         the last-stage maps of run_staged, or the averaged full-resolution maps of run_staged_precise."""
@@ -746,6 +772,28 @@ class Context(object):
                                         ctypes.byref(by)), "op_profile_read")
             out[name] = (ms.value, n.value, fl.value, by.value)
         return out
+
+
+def body_rois(poses, device=0):
+    """Face / hand boxes from poses (P, 18, 3) on the device (op_body_rois), bit-identical to
+    wholebody.body_rois_np: -> (unit (P,) f64, box (P, 3, 4) int32 in the order face, left hand, right
+    hand as (l, t, r, b), state (P, 3) int32: 0 absent, 1 valid, 2 present but not runnable)."""
+    poses = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, N_JOINTS, 3))
+    n = len(poses)
+    unit = np.zeros(n, np.float64)
+    box = np.zeros((n, 3, 4), np.int32)
+    state = np.zeros((n, 3), np.int32)
+    if n:
+        check(lib().op_body_rois(int(device), n, ptr(poses), ptr(unit), ptr(box), ptr(state)), "op_body_rois")
+    return unit, box, state
+
+
+def body_last_ms(device=0):
+    """Device time (upload + kernel, stream events) of the last ``body_rois`` / ``Context.body_rois``
+    that completed on this device."""
+    ms = ctypes.c_double()
+    check(lib().op_body_last_ms(int(device), ctypes.byref(ms)), "op_body_last_ms")
+    return ms.value
 
 
 def cpm_layer_table(arch):
@@ -966,6 +1014,32 @@ class CpmContext(object):
         check(lib().op_cpm_detect_rois(self.h, nf, ptrs, ptr(hs), ptr(ws), ptr(rs), n, ptr(fi), ptr(bx), ptr(mi),
                                        float(thresh), ptr(kp), ptr(found)), "op_cpm_detect_rois")
         return [self._keypoints(kp[i], found[i]) for i in range(n)]
+
+    def detect_rois_staged(self, ctx, first, n_frames, boxes, thresh, frame_ids=None, mirror=None):
+        """``detect_rois`` on staged frames [first, first + n_frames) of the ``Context`` ``ctx``, read
+        where they lie on the device (op_cpm_detect_rois_staged): box i belongs to staged frame
+        ``first + frame_ids[i]`` (default: 0).  Only the tables are uploaded; the ROIs run in chunks
+        of ``set_roi_batch``.  The keypoints of ``detect_rois`` on the same frames, bit for bit."""
+        n, np_ = len(boxes), self.n_maps - 1
+        if n == 0:
+            return []
+        bx = np.ascontiguousarray(np.asarray(boxes, np.int64).reshape(n, 4))
+        if np.any(np.abs(bx) > 2 ** 31 - 1):
+            raise ValueError("op_cpm_detect_rois_staged: box coordinates must fit int32")
+        bx = bx.astype(np.int32)
+        fi = np.zeros(n, np.int32) if frame_ids is None else np.ascontiguousarray(frame_ids, np.int32)
+        mi = np.zeros(n, np.int32) if mirror is None else np.array([int(bool(m)) for m in mirror], np.int32)
+        if len(fi) != n or len(mi) != n:
+            raise ValueError("frame_ids and mirror need one entry per box")
+        kp = np.zeros((n, np_, 3), np.float64)
+        found = np.zeros((n, np_), np.int32)
+        check(lib().op_cpm_detect_rois_staged(self.h, ctx.h, int(first), int(n_frames), n, ptr(fi), ptr(bx), ptr(mi),
+                                              float(thresh), ptr(kp), ptr(found)), "op_cpm_detect_rois_staged")
+        return [self._keypoints(kp[i], found[i]) for i in range(n)]
+
+    def set_roi_batch(self, rois=0):
+        """At most ``rois`` ROIs per forward in ``detect_rois_staged`` (0, the default: all in one)."""
+        check(lib().op_cpm_set_roi_batch(self.h, int(rois)), "op_cpm_set_roi_batch")
 
     def set_roi_group_bytes(self, nbytes=0):
         """Scratch budget of one post-process group of ``detect_rois`` (0: the default)."""

@@ -21,11 +21,17 @@
 //   under a scratch budget and each group takes kRoiGroupLaunches launches over ROIs of different
 //   sizes (resize_planar_rois, cpm_gauss_rois<true|false>, cpm_argmax_rois: the arithmetic of the
 //   per-crop kernels, shared with them); one copy brings every argmax record back.
+// ROI detection on staged frames (op_cpm_detect_rois_staged): the frame table points into the pose
+//   context's staged frames (op_ctx::d_frames), so only the tables are uploaded; the launches wait on
+//   an event of the pose context's stream; with op_cpm_set_roi_batch the ROIs run in consecutive
+//   chunks, each through the same pipeline, and one copy brings every chunk's records back.
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "common.hpp"
+#include "ctx.hpp"
 #include "host_pack.hpp"
 
 namespace op {
@@ -247,6 +253,11 @@ struct op_cpm_ctx {
   std::vector<char> roi_tables;
   bool roi_pending = false;
   int64_t roi_stats[4] = {0, 0, 0, 0};
+  // op_cpm_detect_rois_staged: ROIs per forward (0: all in one), the host images of every chunk's
+  // tables, the event that orders the call behind the pose context's stream
+  int roi_batch = 0;
+  std::vector<std::vector<char>> roi_chunk_tables;
+  hipEvent_t ev_staged = nullptr;
 };
 
 namespace op {
@@ -607,6 +618,7 @@ int op_cpm_destroy(op_cpm_ctx* c) {
   if (c->arena) (void)hipFree(c->arena);
   if (c->scratch) (void)hipFree(c->scratch);
   if (c->d_gauss) (void)hipFree(c->d_gauss);
+  if (c->ev_staged) (void)hipEventDestroy(c->ev_staged);
   splitk_ws_release(c->stream);
   (void)hipStreamDestroy(c->stream);
   delete c;
@@ -918,14 +930,23 @@ struct RoiPlan {
   size_t frames_at = 0, rois_at = 0, planes_at = 0;  // byte offsets of the tables in the image
 };
 
+// Frames that already lie on the device, packed and equal in size (op_cpm_detect_rois_staged): frame
+// f starts `base` + f * h * w * 3 bytes into the buffer the kernels are given.
+struct RoiStaged {
+  int64_t base;
+  int32_t h, w;
+};
+
 // Validates every argument the kernels will index with (OP_ERR_INVALID naming the frame or ROI) and
-// fills *plan and *tables; makes no HIP call.  planes: full-size planes per ROI (maps - 1).
+// fills *plan and *tables; makes no HIP call.  planes: full-size planes per ROI (maps - 1).  With
+// `staged` the frame table describes those frames: no host pointers are looked at and the frame
+// arena stays empty; ROI indices in messages start at roi0 (the chunk's first ROI).
 static int cpm_rois_pack(int32_t n_frames, const uint8_t* const* bgr, const int32_t* fh, const int32_t* fw,
                          const int64_t* row_stride, int32_t n, const int32_t* roi_frame, const int32_t* roi_box,
                          const int32_t* roi_mirror, int planes, int64_t budget, RoiPlan* plan,
-                         std::vector<char>* tables) {
-  const char* who = "op_cpm_detect_rois: ";
-  if (n_frames < 1 || !bgr || !fh || !fw || !row_stride || !roi_frame || !roi_box) {
+                         std::vector<char>* tables, const RoiStaged* staged = nullptr, int roi0 = 0) {
+  const char* who = staged ? "op_cpm_detect_rois_staged: " : "op_cpm_detect_rois: ";
+  if (n_frames < 1 || (!staged && (!bgr || !fh || !fw || !row_stride)) || !roi_frame || !roi_box) {
     set_error(std::string(who) + "bad arguments");
     return OP_ERR_INVALID;
   }
@@ -933,6 +954,12 @@ static int cpm_rois_pack(int32_t n_frames, const uint8_t* const* bgr, const int3
   std::vector<RoiFrame> F(n_frames);
   plan->frame_off.resize(n_frames);
   for (int f = 0; f < n_frames; ++f) {
+    if (staged) {  // validated by the caller; nothing to upload
+      const int64_t packed = (int64_t)staged->w * 3;
+      F[f] = RoiFrame{staged->base + (int64_t)f * packed * staged->h, packed, staged->h, staged->w};
+      plan->frame_off[f] = 0;
+      continue;
+    }
     // 3 * w and every x * 3 + ch of a row stay within int32
     if (!bgr[f] || fh[f] < 1 || fw[f] < 1 || fw[f] > 0x7fffffff / 3 || row_stride[f] < (int64_t)fw[f] * 3) {
       set_error(std::string(who) + "bad frame " + std::to_string(f));
@@ -955,7 +982,7 @@ static int cpm_rois_pack(int32_t n_frames, const uint8_t* const* bgr, const int3
     const int64_t bw = (int64_t)b[2] - b[0], bh = (int64_t)b[3] - b[1];
     ok = ok && bw >= 2 && bh >= 2 && bw * bh < (1ll << 31);
     if (!ok) {
-      set_error(std::string(who) + "bad ROI " + std::to_string(i));
+      set_error(std::string(who) + "bad ROI " + std::to_string(roi0 + i));
       return OP_ERR_INVALID;
     }
     const int mirror = roi_mirror && roi_mirror[i] ? 1 : 0;
@@ -1074,6 +1101,122 @@ int op_cpm_detect_rois(op_cpm_ctx* c, int32_t n_frames, const uint8_t* const* bg
   c->roi_stats[0] = (int64_t)plan.groups.size();
   c->roi_stats[1] = launches;
   c->roi_stats[2] = plan.frame_packed + (int64_t)c->roi_tables.size();
+  c->roi_stats[3] = (int64_t)total;
+  return OP_OK;
+}
+
+int op_cpm_set_roi_batch(op_cpm_ctx* c, int32_t rois) {
+  CRC(cpm_check(c, false));
+  if (rois < 0) {
+    set_error("op_cpm_set_roi_batch: negative ROI count");
+    return OP_ERR_INVALID;
+  }
+  c->roi_batch = rois;
+  return OP_OK;
+}
+
+int op_cpm_detect_rois_staged(op_cpm_ctx* c, op_ctx* ctx, int32_t first, int32_t n_frames, int32_t n,
+                              const int32_t* roi_frame, const int32_t* roi_box, const int32_t* roi_mirror,
+                              float thresh, double* keypoints, int32_t* found) {
+  const char* who = "op_cpm_detect_rois_staged: ";
+  CRC(cpm_check(c, true));
+  if (!ctx || n < 0 || (n > 0 && (!keypoints || !found))) {
+    set_error(std::string(who) + "bad arguments");
+    return OP_ERR_INVALID;
+  }
+  if (ctx->device != c->device) {
+    set_error(std::string(who) + "the two contexts are on different devices");
+    return OP_ERR_INVALID;
+  }
+  if (n == 0) return OP_OK;
+  if (ctx->st_n < 1 || !ctx->d_frames || ctx->st_h < 1 || ctx->st_w < 1 || ctx->st_w > 0x7fffffff / 3) {
+    set_error(std::string(who) + "no staged frames");
+    return OP_ERR_INVALID;
+  }
+  if (first < 0 || n_frames < 1 || first > ctx->st_n - n_frames) {
+    set_error(std::string(who) + "frames " + std::to_string(first) + " .. " + std::to_string((int64_t)first + n_frames - 1) +
+              " are outside the " + std::to_string(ctx->st_n) + " staged frames");
+    return OP_ERR_INVALID;
+  }
+  static_assert(sizeof(RoiFrame) == 24 && sizeof(RoiSrc) == 24 && sizeof(RoiPlane) == 24, "device table layout");
+  const int S = 368;  // as op_cpm_detect
+  const int lh = S / 8, lw = S / 8, ch = c->nm, np = ch - 1;
+  if (c->roi_pending) {  // a call that failed midway: its table images may still be the source of a copy
+    OP_HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->roi_pending = false;
+  }
+  // every chunk's plan and tables first: all arguments are validated before anything is launched
+  const RoiStaged ss{(int64_t)first * ctx->st_h * ctx->st_w * 3, ctx->st_h, ctx->st_w};
+  const int per = c->roi_batch > 0 ? std::min(c->roi_batch, n) : n;
+  const int chunks = (n + per - 1) / per;
+  std::vector<RoiPlan> plans(chunks);
+  c->roi_chunk_tables.assign(chunks, std::vector<char>());
+  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+  size_t tab_bytes = 0, pb = 0;
+  for (int k = 0; k < chunks; ++k) {
+    const int r0 = k * per, cnt = std::min(per, n - r0);
+    CRC(cpm_rois_pack(n_frames, nullptr, nullptr, nullptr, nullptr, cnt, roi_frame + r0, roi_box + 4 * (size_t)r0,
+                      roi_mirror ? roi_mirror + r0 : nullptr, np, c->roi_group_bytes, &plans[k],
+                      &c->roi_chunk_tables[k], &ss, r0));
+    tab_bytes = std::max(tab_bytes, al(c->roi_chunk_tables[k].size()));
+    pb = std::max(pb, al((size_t)plans[k].group_floats * 4));
+  }
+  // scratch: one chunk's tables, every ROI's argmax records, two full-size plane sets of one group
+  const size_t res_off = tab_bytes, pa_off = res_off + al((size_t)n * np * 16);
+  const size_t total = pa_off + 2 * pb;
+  CRC(cpm_geometry(c, per, S, S));  // the largest chunk first: the arena is allocated once
+  CRC(cpm_scratch(c, total));
+  if (!c->ev_staged) OP_HIP_CHECK(hipEventCreateWithFlags(&c->ev_staged, hipEventDisableTiming));
+  // behind the pose context's queued work (the run that took an upload, a draw), without a host wait
+  OP_HIP_CHECK(hipEventRecord(c->ev_staged, ctx->stream));
+  OP_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_staged, 0));
+  char* s = (char*)c->scratch;
+  c->roi_pending = true;
+  float* pa = (float*)(s + pa_off);  // upsampled maps, then the filtered ones
+  float* pt = (float*)(s + pa_off + pb);
+  int32_t* dres = (int32_t*)(s + res_off);
+  int64_t launches = 0, groups = 0, uploaded = 0;
+  for (int k = 0; k < chunks; ++k) {
+    const int r0 = k * per, cnt = std::min(per, n - r0);
+    const RoiPlan& plan = plans[k];
+    const std::vector<char>& tab = c->roi_chunk_tables[k];
+    CRC(cpm_geometry(c, cnt, S, S));
+    OP_HIP_CHECK(hipMemcpyAsync(s, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
+    const RoiFrame* d_frames = (const RoiFrame*)(s + plan.frames_at);
+    const RoiSrc* d_rois = (const RoiSrc*)(s + plan.rois_at);
+    const RoiPlane* d_planes = (const RoiPlane*)(s + plan.planes_at);
+    CRC(launch_preprocess_split_rois(ctx->d_frames, d_frames, d_rois, cnt, S, S, c->buf[X0].p, c->stream, 256.0f));
+    CRC(cpm_run(c));
+    launches += 1;
+    for (const RoiGroup& g : plan.groups) {
+      CRC(launch_resize_rois(c->buf[MAP32].p, c->buf[MAP32].cs, np, lh, lw, d_planes, g.r0, g.cnt, g.blocks, pa,
+                             c->stream));
+      hipLaunchKernelGGL(cpm_gauss_rois<true>, dim3((unsigned)g.blocks), dim3(256), 0, c->stream, pa, np, d_planes, g.r0,
+                         g.cnt, c->d_gauss, c->gauss_r, pt);
+      OP_AFTER_LAUNCH("cpm_gauss_rois_v", c->stream);
+      hipLaunchKernelGGL(cpm_gauss_rois<false>, dim3((unsigned)g.blocks), dim3(256), 0, c->stream, pt, np, d_planes, g.r0,
+                         g.cnt, c->d_gauss, c->gauss_r, pa);
+      OP_AFTER_LAUNCH("cpm_gauss_rois_h", c->stream);
+      // the chunk's records follow those of the chunks before it
+      hipLaunchKernelGGL(cpm_argmax_rois, dim3((unsigned)(g.cnt * np)), dim3(kArgT), 0, c->stream, pa, np, d_planes, g.r0,
+                         dres + (size_t)r0 * np * 4);
+      OP_AFTER_LAUNCH("cpm_argmax_rois", c->stream);
+      OP_HIP_CHECK(hipGetLastError());
+      launches += kRoiGroupLaunches;
+    }
+    groups += (int64_t)plan.groups.size();
+    uploaded += (int64_t)tab.size();
+  }
+  std::vector<int32_t> res((size_t)n * np * 4);
+  OP_HIP_CHECK(hipMemcpyAsync(res.data(), dres, res.size() * 4, hipMemcpyDeviceToHost, c->stream));
+  OP_HIP_CHECK(hipStreamSynchronize(c->stream));
+  c->roi_pending = false;
+  for (int i = 0; i < n; ++i)
+    cpm_peaks_decode(res.data() + (size_t)i * np * 4, ch, roi_box[4 * (size_t)i + 2] - roi_box[4 * (size_t)i],
+                     thresh, keypoints + (size_t)i * np * 3, found + (size_t)i * np);
+  c->roi_stats[0] = groups;
+  c->roi_stats[1] = launches;
+  c->roi_stats[2] = uploaded;
   c->roi_stats[3] = (int64_t)total;
   return OP_OK;
 }

@@ -8,6 +8,10 @@ a plumbing run without trained weights), runs PoseDetector on the image, blends 
 (``cv2.addWeighted(img, 0.6, pose, 0.4, 0)``), then for every person crops the face and the hands
 (PoseDetector.get_unit_length / crop_face / crop_hands), runs FaceDetector / HandDetector on the
 crops and draws their keypoints and white crop rectangles; writes result.png.
+
+``--img`` may be given several times; ``--staged`` takes the images (all of one size) through the
+staged batch instead (``run_batch``: one staged pose step, ``wholebody.detect_staged``, one device
+draw) and writes result.png for one image, result_<k>.png for several.
 """
 import argparse
 import os
@@ -98,9 +102,34 @@ def run(img, pose_detector, face_detector, hand_detector, log=print, device_draw
     return res_img
 
 
+def run_batch(frames, pose_detector, face_detector, hand_detector, log=print, device_draw=True, roi_batch=128):
+    """``run`` for a batch of equally sized frames without leaving the device between the steps:
+    the frames are staged once, the pose step runs on all of them (``PoseDetector.run_staged``),
+    ``wholebody.detect_staged`` makes the boxes on the device from the poses where they lie and runs
+    FaceNet / HandNet on the staged frames in place, and every frame's drawing (``render.demo_list``)
+    is painted in one ``render.render_staged`` call (``device_draw=False``: ``render.render_np`` per
+    frame, the same pixels).  -> the list of result images.  A box the ROI detector cannot run is
+    left out of the drawing (``run`` would raise there)."""
+    from . import render, wholebody
+    frames = np.ascontiguousarray(np.stack([np.asarray(f) for f in frames]))
+    log("Estimating pose...")
+    n = pose_detector.run_staged(frames)
+    log("Estimating face and hands keypoints...")
+    result = wholebody.detect_staged(pose_detector, face_detector, hand_detector, 0, n, roi_batch=roi_batch)
+    drawn = lambda item: item if item is not None and item[0] is not None else None  # skipped boxes are not drawn
+    lists = []
+    for persons in result:
+        poses = np.array([p["pose"] for p in persons]).reshape(-1, 18, 3)
+        lists.append(render.demo_list(poses, [drawn(p["face"]) for p in persons],
+                                      [{side: drawn(p["hands"][side]) for side in ("left", "right")} for p in persons]))
+    if device_draw:
+        return list(render.render_staged(pose_detector.staged_context(), 0, n, lists))
+    return [render.render_np(f, l) for f, l in zip(frames, lists)]
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Pose detector")
-    ap.add_argument("--img", help="image file path")
+    ap.add_argument("--img", action="append", help="image file path (may be given several times)")
     ap.add_argument("--gpu", "-g", type=int, default=-1, help="HIP device (negative: device 0; no CPU path)")
     ap.add_argument("--models", default="models", help="directory of coco_posenet.npz / handnet.npz / facenet.npz")
     ap.add_argument("--random-weights", action="store_true", help="seeded random weights (plumbing run)")
@@ -108,19 +137,32 @@ def main(argv=None):
     ap.add_argument("--device-draw", action="store_true", help="draw on the device (one display list, one launch)")
     ap.add_argument("--device-crops", action="store_true",
                     help="cut the face / hand crops on the device from the image and the boxes (detect_rois)")
+    ap.add_argument("--staged", action="store_true",
+                    help="the staged batch: poses, boxes, face / hand keypoints and drawing without leaving the device")
     args = ap.parse_args(argv)
+    if not args.img:
+        ap.error("--img is required")
+    pose_kw = {"max_batch": len(args.img)} if args.staged else {}
     if args.random_weights:
-        pd = PoseDetector("posenet", model=_weights.random_weights(0), device=args.gpu)
+        pd = PoseDetector("posenet", model=_weights.random_weights(0), device=args.gpu, **pose_kw)
         hd = HandDetector("handnet", model=_weights.random_weights(0, arch="handnet"), device=args.gpu)
         fd = FaceDetector("facenet", model=_weights.random_weights(0, arch="facenet"), device=args.gpu)
     else:
-        pd = PoseDetector("posenet", os.path.join(args.models, "coco_posenet.npz"), device=args.gpu)
+        pd = PoseDetector("posenet", os.path.join(args.models, "coco_posenet.npz"), device=args.gpu, **pose_kw)
         hd = HandDetector("handnet", os.path.join(args.models, "handnet.npz"), device=args.gpu)
         fd = FaceDetector("facenet", os.path.join(args.models, "facenet.npz"), device=args.gpu)
-    img = read_bgr(args.img)
-    res_img = run(img, pd, fd, hd, device_draw=args.device_draw, device_crops=args.device_crops)
-    print("Saving result into %s..." % args.out)
-    write_bgr(args.out, res_img)
+    imgs = [read_bgr(path) for path in args.img]
+    if args.staged:
+        if len({im.shape for im in imgs}) != 1:
+            ap.error("--staged needs images of one size")
+        res_imgs = run_batch(imgs, pd, fd, hd)
+    else:
+        res_imgs = [run(img, pd, fd, hd, device_draw=args.device_draw, device_crops=args.device_crops) for img in imgs]
+    stem, ext = os.path.splitext(args.out)
+    for k, res_img in enumerate(res_imgs):
+        out = args.out if len(res_imgs) == 1 else "%s_%d%s" % (stem, k, ext)
+        print("Saving result into %s..." % out)
+        write_bgr(out, res_img)
     return 0
 
 

@@ -73,6 +73,17 @@ class FaceDetector(object):
         the device (op_cpm_detect_rois, roi_crop_np), each frame is uploaded once."""
         return self._ctx.detect_rois(imgs, bboxes, params["face_heatmap_peak_thresh"], frame_ids=frame_ids)
 
+    def detect_rois_staged(self, pose_ctx, first, n_frames, bboxes, frame_ids=None):
+        """``detect_rois`` on staged frames [first, first + n_frames) of the pose ``_lib.Context``
+        ``pose_ctx``, read in place on the device (op_cpm_detect_rois_staged): ``frame_ids[i]``
+        counts from ``first``.  Nothing but the tables is uploaded."""
+        return self._ctx.detect_rois_staged(pose_ctx, first, n_frames, bboxes, params["face_heatmap_peak_thresh"],
+                                            frame_ids=frame_ids)
+
+    def set_roi_batch(self, rois=0):
+        """At most ``rois`` ROIs per forward in ``detect_rois_staged`` (0: all in one)."""
+        self._ctx.set_roi_batch(rois)
+
 
 def draw_face_keypoints(orig_img, face_keypoints, left_top):
     """face_detector.py:86-102: radius-2 discs and 1-px lines in (255, 255, 0) (BGR)."""

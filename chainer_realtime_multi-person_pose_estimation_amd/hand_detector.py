@@ -60,6 +60,17 @@ class HandDetector(object):
         return self._ctx.detect_rois(imgs, bboxes, params["hand_heatmap_peak_thresh"], frame_ids=frame_ids,
                                      mirror=[t == "left" for t in hand_types])
 
+    def detect_rois_staged(self, pose_ctx, first, n_frames, bboxes, hand_types, frame_ids=None):
+        """``detect_rois`` on staged frames [first, first + n_frames) of the pose ``_lib.Context``
+        ``pose_ctx``, read in place on the device (op_cpm_detect_rois_staged): ``frame_ids[i]``
+        counts from ``first``; a ``"left"`` box is read mirrored.  Nothing but the tables is uploaded."""
+        return self._ctx.detect_rois_staged(pose_ctx, first, n_frames, bboxes, params["hand_heatmap_peak_thresh"],
+                                            frame_ids=frame_ids, mirror=[t == "left" for t in hand_types])
+
+    def set_roi_batch(self, rois=0):
+        """At most ``rois`` ROIs per forward in ``detect_rois_staged`` (0: all in one)."""
+        self._ctx.set_roi_batch(rois)
+
 
 def draw_hand_keypoints(orig_img, hand_keypoints, left_top):
     """hand_detector.py:96-116: per finger, radius-3 discs on both ends and a 1-px line."""

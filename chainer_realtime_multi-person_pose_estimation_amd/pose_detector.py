@@ -44,8 +44,9 @@ class PoseDetector(object):
         if model is None and arch not in (None, "posenet"):
             raise ValueError("arch %r is not on this path (only 'posenet')" % (arch,))
         self.device = 0 if device is None or device < 0 else int(device)
+        self.max_batch = int(max_batch)
         limits = _lib.OpLimits()
-        limits.max_batch = int(max_batch)
+        limits.max_batch = self.max_batch
         self._ctx = _lib.Context(self.device, _lib.params_from_dict(params), limits)
         self._ctx.set_precision(precision)
         if batch_invariant:  # one accumulation order for every batch size (op_set_batch_invariant)
@@ -160,6 +161,25 @@ class PoseDetector(object):
         if res.n_persons == 0:
             return np.array([]), np.empty(0)
         return poses, scores
+
+    # ---- the staged batch (wholebody.detect_staged, demo.run_batch) ----
+    def staged_context(self):
+        """The ``_lib.Context`` whose staged frames and result rows the staged entry points read."""
+        return self._ctx
+
+    def run_staged(self, frames):
+        """Stage ``frames`` (n, h, w, 3) uint8 and run ``__call__``'s path (``detect_precise``'s when
+        ``precise``) on all of them in one step; the poses stay on the device
+        (``staged_context().fetch_results`` brings them back).  -> n."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.ndim != 4 or frames.shape[3] != 3:
+            raise ValueError("expected (n, h, w, 3) uint8 BGR frames")
+        self._ctx.stage_frames(frames)
+        if self.precise:
+            self._ctx.run_staged_precise()
+        else:
+            self._ctx.run_staged()
+        return len(frames)
 
     # ---- crops for the face / hand detectors (restating pose_detector.py:266-425; host-side, used
     # by demo.py).  The arithmetic follows the reference operation for operation (the crop SHA-256

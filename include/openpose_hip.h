@@ -494,6 +494,24 @@ int op_cpm_set_roi_group_bytes(op_cpm_ctx* ctx, int64_t bytes);
 /* The last successful op_cpm_detect_rois: out = {groups, launches outside the forward, bytes uploaded
  * (packed frames + tables), scratch bytes laid out}. */
 int op_cpm_roi_stats(op_cpm_ctx* ctx, int64_t out[4]);
+/* op_cpm_detect_rois with the frames where ctx staged them (op_stage_frames, or the frames an
+ * op_run_staged* took from op_upload_frames): ROI i is a box of staged frame first + roi_frame[i]
+ * (roi_frame in [0, n_frames)), read in place; nothing but the tables (24 B per frame, 48 B per ROI)
+ * is uploaded.  The launches run on cpm's stream behind an event recorded on ctx's stream (no host
+ * synchronisation for the ordering); the call itself returns synchronised, so the frames need no
+ * protection from a later stage or upload.  With op_cpm_set_roi_batch the ROIs run in consecutive
+ * chunks, one forward each.  Results as op_cpm_detect_rois on the same frames given from the host,
+ * bit for bit (with op_cpm_set_batch_invariant also across chunk sizes).  OP_ERR_INVALID before any
+ * launch for: contexts on different devices, no staged set, frames [first, first + n_frames) outside
+ * the staged set, and the ROI checks of op_cpm_detect_rois.  n == 0: OP_OK.  op_cpm_roi_stats then
+ * reports the sums over the chunks; its bytes uploaded are 24 n_frames + 48 (ROIs of the chunk) per
+ * chunk: no pixel bytes. */
+int op_cpm_detect_rois_staged(op_cpm_ctx* cpm, op_ctx* ctx, int32_t first, int32_t n_frames, int32_t n,
+                              const int32_t* roi_frame, const int32_t* roi_box, const int32_t* roi_mirror,
+                              float thresh, double* keypoints, int32_t* found);
+/* At most `rois` ROIs per forward in op_cpm_detect_rois_staged (0, the default: all in one, as
+ * op_cpm_detect_rois); the activation arena and the scratch are sized to the largest chunk. */
+int op_cpm_set_roi_batch(op_cpm_ctx* cpm, int32_t rois);
 
 /* ---- Training iteration: Updater.update_core of train_coco_pose_estimation.py:93-123 ----
  * One context = CocoPoseNet master weights (f32), Adam state and every activation of a batch of n
@@ -789,6 +807,31 @@ int op_overlay_staged(op_ctx* ctx, int32_t first, int32_t n, int32_t layers, con
 /* Device time (ms, stream events) of the uploads and the kernel of the last op_overlay or
  * op_overlay_staged that completed on `device`; OP_ERR_STATE before the first. */
 int op_overlay_last_ms(int32_t device, double* ms);
+
+/* ---- Face / hand boxes from poses (wholebody.py; pose_detector.py:267-297, 354-399) ----
+ * One kernel, one thread per person, f64 with every operation rounded on its own: unit =
+ * PoseDetector.get_unit_length, box[p][0] = the face box of crop_face, box[p][1] / box[p][2] the left /
+ * right hand boxes of crop_hands, each (l, t, r, b) truncated toward zero.  state: 0 absent (no nose /
+ * no hand), 1 valid, 2 present but not runnable: a coordinate that is not finite or beyond +-2^30,
+ * r-l < 2, b-t < 2 or (r-l) * (b-t) >= 2^31, exactly what op_cpm_detect_rois refuses; a box of state 0
+ * or 2 is zeros.  The shift of the hand joints (0.3 of elbow -> hand) stays in registers: the poses are
+ * not written.  Bit-identical to wholebody.body_rois_np.
+ * poses (n_persons, 18, 3) f64 from the host -> unit (n_persons), box (n_persons, 3, 4), state
+ * (n_persons, 3).  n_persons == 0: OP_OK. */
+int op_body_rois(int32_t device, int32_t n_persons, const double* poses, double* unit, int32_t* box,
+                 int32_t* state);
+/* The same for the result rows of staged frames [first, first + n) where they lie on the device,
+ * after ctx's queued work; persons of frame i are rows [i * cap, i * cap + min(count[i], cap)) of the
+ * outputs (unit n * cap, box n * cap * 12, state n * cap * 3).  count[i] = persons found (may exceed
+ * cap: OP_ERR_CAPACITY with the rows needed in count, as op_fetch_results); frame_status[i] = the
+ * frame's status (a frame over the batched post-process caps has OP_ERR_CAPACITY and count 0 here: the
+ * caller takes it through op_fetch_result and op_body_rois).  Only the headers and these tables come
+ * back (one asynchronous copy, one synchronisation); the result rows are neither copied nor written. */
+int op_body_rois_staged(op_ctx* ctx, int32_t first, int32_t n, int32_t cap, int32_t* count,
+                        int32_t* frame_status, double* unit, int32_t* box, int32_t* state);
+/* Device time (ms, stream events) of the uploads and the kernel of the last op_body_rois or
+ * op_body_rois_staged that completed on `device`; OP_ERR_STATE before the first. */
+int op_body_last_ms(int32_t device, double* ms);
 
 #ifdef __cplusplus
 }
