@@ -20,10 +20,10 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
 #include "common.hpp"
+#include "oneshot.hpp"
 
 namespace op {
 namespace {
@@ -35,7 +35,6 @@ constexpr int kMaskPitch = kBox + 4;
 constexpr int kWarpBorder = 128;  // saturate_cast<uchar>(127.5)
 constexpr int kCropPad = 127;     // (zeros + 127.5).astype('uint8')
 constexpr int kMaxSide = 16384;
-constexpr int kMaxDevices = 64;
 
 struct AugSample {
   int64_t src_off, msk_off;  // into the uploaded sources / masks (msk_off < 0: no mask)
@@ -360,10 +359,7 @@ void linear_axis(int dsize, int ssize, bool clamp, std::vector<int32_t>* out) {
   }
 }
 
-int aug_invalid(const std::string& msg) {
-  set_error("op_augment: " + msg);
-  return OP_ERR_INVALID;
-}
+const char* const kAug = "op_augment";
 
 struct AugHost {
   std::vector<AugSample> samples;
@@ -375,33 +371,33 @@ struct AugHost {
 int augment_pack(int32_t n, const uint8_t* const* bgr, const int64_t* row_stride, const uint8_t* const* mask,
                  const op_augment_plan* plans, int32_t insize, const uint8_t* out_bgr, const uint8_t* out_mask,
                  AugHost* out) {
-  if (n < 1 || n > 65535) return aug_invalid("n must be in 1 .. 65535");
-  if (insize < 1 || insize > kMaxSide) return aug_invalid("insize must be in 1 .. 16384");
-  if (!bgr) return aug_invalid("null bgr array");
-  if (!row_stride) return aug_invalid("null row_stride array");
-  if (!plans) return aug_invalid("null plans array");
-  if (!out_bgr) return aug_invalid("null out_bgr");
-  if (!out_mask) return aug_invalid("null out_mask");
+  if (n < 1 || n > 65535) return invalid(kAug, "n must be in 1 .. 65535");
+  if (insize < 1 || insize > kMaxSide) return invalid(kAug, "insize must be in 1 .. 16384");
+  if (!bgr) return invalid(kAug, "null bgr array");
+  if (!row_stride) return invalid(kAug, "null row_stride array");
+  if (!plans) return invalid(kAug, "null plans array");
+  if (!out_bgr) return invalid(kAug, "null out_bgr");
+  if (!out_mask) return invalid(kAug, "null out_mask");
   for (int f = 0; f < n; ++f) {
     const op_augment_plan& p = plans[f];
     const std::string at = "plan " + std::to_string(f) + ": ";
-    if (!bgr[f]) return aug_invalid(at + "null bgr entry");
-    if (p.insize != insize) return aug_invalid(at + "insize differs from the call's");
-    if (p.h < 1 || p.w < 1 || p.h > kMaxSide || p.w > kMaxSide) return aug_invalid(at + "h, w must be in 1 .. 16384");
-    if (row_stride[f] < (int64_t)p.w * 3) return aug_invalid(at + "row_stride below 3 * w");
-    if (p.rw < 1 || p.rh < 1 || p.rw > kMaxSide || p.rh > kMaxSide) return aug_invalid(at + "rw, rh must be in 1 .. 16384");
-    if (p.bw < 1 || p.bh < 1 || p.bw > kMaxSide || p.bh > kMaxSide) return aug_invalid(at + "bw, bh must be in 1 .. 16384");
+    if (!bgr[f]) return invalid(kAug, at + "null bgr entry");
+    if (p.insize != insize) return invalid(kAug, at + "insize differs from the call's");
+    if (p.h < 1 || p.w < 1 || p.h > kMaxSide || p.w > kMaxSide) return invalid(kAug, at + "h, w must be in 1 .. 16384");
+    if (row_stride[f] < (int64_t)p.w * 3) return invalid(kAug, at + "row_stride below 3 * w");
+    if (p.rw < 1 || p.rh < 1 || p.rw > kMaxSide || p.rh > kMaxSide) return invalid(kAug, at + "rw, rh must be in 1 .. 16384");
+    if (p.bw < 1 || p.bh < 1 || p.bw > kMaxSide || p.bh > kMaxSide) return invalid(kAug, at + "bw, bh must be in 1 .. 16384");
     for (int k = 0; k < 6; ++k)
-      if (!std::isfinite(p.R[k])) return aug_invalid(at + "non-finite matrix R");
+      if (!std::isfinite(p.R[k])) return invalid(kAug, at + "non-finite matrix R");
     if ((int64_t)p.x2 - p.x1 != (int64_t)p.x_to - p.x_from || (int64_t)p.y2 - p.y1 != (int64_t)p.y_to - p.y_from)
-      return aug_invalid(at + "the copy window's two sides differ in size");
+      return invalid(kAug, at + "the copy window's two sides differ in size");
     const bool empty = p.x2 < p.x1 || p.y2 < p.y1;
     if (!empty && (p.x_from < 0 || p.x_to >= insize || p.y_from < 0 || p.y_to >= insize))
-      return aug_invalid(at + "the copy window does not fit insize");
+      return invalid(kAug, at + "the copy window does not fit insize");
     if (!empty && (p.x1 < 0 || p.x2 >= p.bw || p.y1 < 0 || p.y2 >= p.bh))
-      return aug_invalid(at + "the copy window does not fit the rotated size bw x bh");
+      return invalid(kAug, at + "the copy window does not fit the rotated size bw x bh");
     if (p.colour && (std::abs((int64_t)p.dh) > 10 || std::abs((int64_t)p.ds) > 40 || std::abs((int64_t)p.dv) > 30))
-      return aug_invalid(at + "colour deltas dh, ds, dv outside [-10, 10], [-40, 40], [-30, 30]");
+      return invalid(kAug, at + "colour deltas dh, ds, dv outside [-10, 10], [-40, 40], [-30, 30]");
   }
   out->samples.resize(n);
   for (int f = 0; f < n; ++f) {
@@ -463,7 +459,7 @@ int augment_pack(int32_t n, const uint8_t* const* bgr, const int64_t* row_stride
       wt[2 * insize + r] = (int32_t)(rint_i32((M[1] * y + M[2]) * 1024.0) + 16);
       wt[3 * insize + r] = (int32_t)(rint_i32((M[4] * y + M[5]) * 1024.0) + 16);
     }
-    if (out->itab.size() > ((size_t)1 << 30)) return aug_invalid("tables too large");
+    if (out->itab.size() > ((size_t)1 << 30)) return invalid(kAug, "tables too large");
   }
   const AugTables& t = aug_tables();
   out->hsv_off = (int32_t)out->itab.size();
@@ -472,10 +468,8 @@ int augment_pack(int32_t n, const uint8_t* const* bgr, const int64_t* row_stride
   return OP_OK;
 }
 
-std::mutex g_aug_mutex;
-double g_aug_ms[kMaxDevices];
-long long g_aug_counts[kMaxDevices][2];
-bool g_aug_ran[kMaxDevices];
+LastMs g_aug_last;
+long long g_aug_counts[kMaxDevices][2];  // the LDS / fallback paths of the last call, under g_aug_last.mutex
 
 }  // namespace
 }  // namespace op
@@ -497,118 +491,72 @@ extern "C" int op_augment(int32_t device, int32_t n, const uint8_t* const* bgr, 
   AugHost ah;
   const int rc = augment_pack(n, bgr, row_stride, mask, plans, insize, out_bgr, out_mask, &ah);
   if (rc) return rc;
-  int ndev = 0;
-  OP_HIP_CHECK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev || device >= kMaxDevices) {
-    set_error("op_augment: no HIP device " + std::to_string(device));
-    return OP_ERR_INVALID;
-  }
-  OP_HIP_CHECK(hipSetDevice(device));
+  const int rd = use_device(kAug, device);
+  if (rd) return rd;
   const AugTables& t = aug_tables();
   const size_t plane = (size_t)insize * insize;
-  enum { SAMPLES, ITAB, CUBIC, LINEAR, SRC, MSK, RS, RM, OUT, OMASK, COUNTS, NBUF };
-  const size_t sizes[NBUF] = {ah.samples.size() * sizeof(AugSample), ah.itab.size() * sizeof(int32_t),
-                              t.cubic.size() * sizeof(int16_t), t.linear.size() * sizeof(int16_t),
-                              (size_t)ah.src_bytes, (size_t)ah.msk_bytes, (size_t)ah.rs_bytes, (size_t)ah.rm_bytes,
-                              n * plane * 3, n * plane, 2 * sizeof(unsigned long long)};
-  void* d[NBUF] = {};
-  hipEvent_t ev[2] = {};
-  int res = OP_OK;
-  auto fail = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess || res) return;
-    set_error(std::string("op_augment: ") + what + ": " + hipGetErrorString(e));
-    res = OP_ERR_HIP;
-  };
-  for (int i = 0; i < NBUF && !res; ++i)
-    if (sizes[i]) fail(hipMalloc(&d[i], sizes[i]), "hipMalloc");
-  for (int i = 0; i < 2 && !res; ++i) fail(hipEventCreate(&ev[i]), "hipEventCreate");
-  if (!res) fail(hipEventRecord(ev[0], nullptr), "hipEventRecord");
-  if (!res) fail(hipMemcpy(d[SAMPLES], ah.samples.data(), sizes[SAMPLES], hipMemcpyHostToDevice), "samples upload");
-  if (!res) fail(hipMemcpy(d[ITAB], ah.itab.data(), sizes[ITAB], hipMemcpyHostToDevice), "tables upload");
-  if (!res) fail(hipMemcpy(d[CUBIC], t.cubic.data(), sizes[CUBIC], hipMemcpyHostToDevice), "cubic table upload");
-  if (!res) fail(hipMemcpy(d[LINEAR], t.linear.data(), sizes[LINEAR], hipMemcpyHostToDevice), "linear table upload");
-  if (!res) fail(hipMemset(d[COUNTS], 0, sizes[COUNTS]), "hipMemset");
-  for (int f = 0; f < n && !res; ++f) {
+  const size_t cubic_bytes = t.cubic.size() * sizeof(int16_t), linear_bytes = t.linear.size() * sizeof(int16_t);
+  unsigned long long counts[2] = {0, 0};
+  Job job(kAug, nullptr);
+  AugArgs a;
+  a.samples = (const AugSample*)job.alloc(ah.samples.size() * sizeof(AugSample));
+  a.itab = (const int32_t*)job.alloc(ah.itab.size() * sizeof(int32_t));
+  a.cubic = (const int16_t*)job.alloc(cubic_bytes);
+  a.linear = (const int16_t*)job.alloc(linear_bytes);
+  uint8_t* src = (uint8_t*)job.alloc((size_t)ah.src_bytes);
+  uint8_t* msk = (uint8_t*)job.alloc((size_t)ah.msk_bytes);
+  a.src = src;
+  a.msk = msk;
+  a.rs = (uint8_t*)job.alloc((size_t)ah.rs_bytes);
+  a.rm = (uint8_t*)job.alloc((size_t)ah.rm_bytes);
+  a.out_bgr = (uint8_t*)job.alloc(n * plane * 3);
+  a.out_mask = (uint8_t*)job.alloc(n * plane);
+  a.counts = (unsigned long long*)job.alloc(sizeof(counts));
+  a.hsv_off = ah.hsv_off;
+  a.insize = insize;
+  job.begin();
+  job.upload((void*)a.samples, ah.samples.data(), ah.samples.size() * sizeof(AugSample), "samples upload");
+  job.upload((void*)a.itab, ah.itab.data(), ah.itab.size() * sizeof(int32_t), "tables upload");
+  job.upload((void*)a.cubic, t.cubic.data(), cubic_bytes, "cubic table upload");
+  job.upload((void*)a.linear, t.linear.data(), linear_bytes, "linear table upload");
+  job.memset(a.counts, 0, sizeof(counts));
+  for (int f = 0; f < n && job.ok(); ++f) {
     const AugSample& s = ah.samples[f];
-    fail(hipMemcpy2D((uint8_t*)d[SRC] + s.src_off, (size_t)s.w * 3, bgr[f], (size_t)row_stride[f], (size_t)s.w * 3,
-                     (size_t)s.h, hipMemcpyHostToDevice), "image upload");
-    if (!res && s.msk_off >= 0)
-      fail(hipMemcpy((uint8_t*)d[MSK] + s.msk_off, mask[f], (size_t)s.h * s.w, hipMemcpyHostToDevice), "mask upload");
+    job.upload2d(src + s.src_off, (size_t)s.w * 3, bgr[f], (size_t)row_stride[f], (size_t)s.w * 3, (size_t)s.h,
+                 "image upload");
+    if (s.msk_off >= 0) job.upload(msk + s.msk_off, mask[f], (size_t)s.h * s.w, "mask upload");
   }
-  if (!res) {
-    AugArgs a;
-    a.samples = (const AugSample*)d[SAMPLES];
-    a.itab = (const int32_t*)d[ITAB];
-    a.cubic = (const int16_t*)d[CUBIC];
-    a.linear = (const int16_t*)d[LINEAR];
-    a.src = (const uint8_t*)d[SRC];
-    a.msk = (const uint8_t*)d[MSK];
-    a.rs = (uint8_t*)d[RS];
-    a.rm = (uint8_t*)d[RM];
-    a.out_bgr = (uint8_t*)d[OUT];
-    a.out_mask = (uint8_t*)d[OMASK];
-    a.counts = (unsigned long long*)d[COUNTS];
-    a.hsv_off = ah.hsv_off;
-    a.insize = insize;
+  if (job.ok()) {
     hipLaunchKernelGGL(aug_resize, dim3((unsigned)((ah.max_pix + 255) / 256), (unsigned)n), dim3(256), 0, nullptr, a);
-    fail(hipGetLastError(), "aug_resize");
+    job.check(hipGetLastError(), "aug_resize");
     const unsigned tiles = (unsigned)((insize + kTile - 1) / kTile);
     hipLaunchKernelGGL(aug_fused, dim3(tiles, tiles, (unsigned)n), dim3(kTile, kTile), 0, nullptr, a);
-    fail(hipGetLastError(), "aug_fused");
+    job.check(hipGetLastError(), "aug_fused");
   }
-  if (!res) fail(hipEventRecord(ev[1], nullptr), "hipEventRecord");
-  if (!res) fail(hipDeviceSynchronize(), "kernels");
-  float ms = 0.0f;
-  unsigned long long counts[2] = {0, 0};
-  if (!res) fail(hipEventElapsedTime(&ms, ev[0], ev[1]), "hipEventElapsedTime");
-  if (!res) fail(hipMemcpy(counts, d[COUNTS], sizes[COUNTS], hipMemcpyDeviceToHost), "counts download");
-  if (!res) fail(hipMemcpy(out_bgr, d[OUT], sizes[OUT], hipMemcpyDeviceToHost), "image download");
-  if (!res) fail(hipMemcpy(out_mask, d[OMASK], sizes[OMASK], hipMemcpyDeviceToHost), "mask download");
-  for (void* p : d)
-    if (p) (void)hipFree(p);
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  if (!res) {
-    std::lock_guard<std::mutex> lock(g_aug_mutex);
-    g_aug_ms[device] = (double)ms;
+  job.end();
+  job.finish("kernels");
+  job.download(counts, a.counts, sizeof(counts), "counts download");
+  job.download(out_bgr, a.out_bgr, n * plane * 3, "image download");
+  job.download(out_mask, a.out_mask, n * plane, "mask download");
+  if (job.ok()) {
+    std::lock_guard<std::mutex> lock(g_aug_last.mutex);
+    g_aug_last.ms[device] = (double)job.ms();
+    g_aug_last.ran[device] = true;
     g_aug_counts[device][0] = (long long)counts[0];
     g_aug_counts[device][1] = (long long)counts[1];
-    g_aug_ran[device] = true;
   }
-  return res;
-}
-
-static int aug_last(const char* who, int32_t device) {
-  if (device < 0 || device >= kMaxDevices) {
-    set_error(std::string(who) + ": bad device " + std::to_string(device));
-    return OP_ERR_INVALID;
-  }
-  if (!g_aug_ran[device]) {
-    set_error(std::string(who) + ": no op_augment has completed on device " + std::to_string(device));
-    return OP_ERR_STATE;
-  }
-  return OP_OK;
+  return job.status();
 }
 
 extern "C" int op_augment_last_ms(int32_t device, double* ms) {
-  if (!ms) {
-    set_error("op_augment_last_ms: null ms");
-    return OP_ERR_INVALID;
-  }
-  std::lock_guard<std::mutex> lock(g_aug_mutex);
-  const int rc = aug_last("op_augment_last_ms", device);
-  if (rc) return rc;
-  *ms = g_aug_ms[device];
-  return OP_OK;
+  return g_aug_last.get("op_augment_last_ms", kAug, device, ms);
 }
 
 extern "C" int op_augment_last_paths(int32_t device, int64_t* counts) {
-  if (!counts) {
-    set_error("op_augment_last_paths: null counts");
-    return OP_ERR_INVALID;
-  }
-  std::lock_guard<std::mutex> lock(g_aug_mutex);
-  const int rc = aug_last("op_augment_last_paths", device);
+  const char* who = "op_augment_last_paths";
+  if (!counts) return invalid(who, "null counts");
+  std::lock_guard<std::mutex> lock(g_aug_last.mutex);
+  const int rc = g_aug_last.check(who, kAug, device);
   if (rc) return rc;
   counts[0] = g_aug_counts[device][0];
   counts[1] = g_aug_counts[device][1];

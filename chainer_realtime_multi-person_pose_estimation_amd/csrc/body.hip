@@ -16,17 +16,16 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "common.hpp"
 #include "ctx.hpp"
+#include "oneshot.hpp"
 
 namespace op {
 namespace {
 
-constexpr int kBodyMaxDevices = 64;
 constexpr int kBodyThreads = 64;
 constexpr int64_t kBodyMaxRows = 1ll << 24;  // persons (host) or frames * cap (staged) of one call
 constexpr int kPose = OP_N_JOINTS * 3;       // doubles per person row
@@ -155,11 +154,6 @@ __global__ __launch_bounds__(kBodyThreads) void body_rois_kernel(BodyArgs a) {
   }
 }
 
-int body_invalid(const char* who, const std::string& msg) {
-  set_error(std::string(who) + ": " + msg);
-  return OP_ERR_INVALID;
-}
-
 // params['limbs_point'] as the library holds it (op_default_params), checked before the kernel indexes with it
 int body_limbs(const char* who, int32_t (*limb)[2]) {
   op_params prm;
@@ -168,22 +162,13 @@ int body_limbs(const char* who, int32_t (*limb)[2]) {
   for (int i = 0; i < OP_N_LIMBS; ++i)
     for (int e = 0; e < 2; ++e) {
       if (prm.limbs_point[i][e] < 0 || prm.limbs_point[i][e] >= OP_N_JOINTS)
-        return body_invalid(who, "limbs_point names a joint outside 0 .. 17");
+        return invalid(who, "limbs_point names a joint outside 0 .. 17");
       limb[i][e] = prm.limbs_point[i][e];
     }
   return OP_OK;
 }
 
-std::mutex g_body_mutex;
-double g_body_ms[kBodyMaxDevices];
-bool g_body_ran[kBodyMaxDevices];
-
-void body_done(int device, float ms) {
-  if (device < 0 || device >= kBodyMaxDevices) return;
-  std::lock_guard<std::mutex> lock(g_body_mutex);
-  g_body_ms[device] = (double)ms;
-  g_body_ran[device] = true;
-}
+LastMs g_body_last;
 
 // The output block of one call, one allocation and one copy back: [count | status] (staged only),
 // units, boxes, states, in this order, the f64 part 8-byte aligned.
@@ -204,6 +189,20 @@ struct BodyBlock {
   }
 };
 
+// Queues body_rois_kernel over a's n_frames x cap rows, writing blk's block at d_out, and the block's
+// copy into `host`; ends the job's timing
+void body_run(Job& job, BodyArgs& a, const BodyBlock& blk, char* d_out, std::vector<char>& host) {
+  if (job.ok()) {
+    const int64_t rows = (int64_t)a.n_frames * a.cap;
+    blk.point(&a, d_out);
+    hipLaunchKernelGGL(body_rois_kernel, dim3((unsigned)((rows + kBodyThreads - 1) / kBodyThreads)), dim3(kBodyThreads),
+                       0, job.stream(), a);
+    job.check(hipGetLastError(), "body_rois_kernel");
+  }
+  job.end();
+  job.download(host.data(), d_out, blk.bytes);
+}
+
 }  // namespace
 }  // namespace op
 
@@ -212,126 +211,67 @@ using namespace op;
 extern "C" int op_body_rois(int32_t device, int32_t n_persons, const double* poses, double* unit, int32_t* box,
                             int32_t* state) {
   const char* who = "op_body_rois";
-  if (n_persons < 0 || n_persons > kBodyMaxRows) return body_invalid(who, "n_persons must be in 0 .. 16777216");
+  if (n_persons < 0 || n_persons > kBodyMaxRows) return invalid(who, "n_persons must be in 0 .. 16777216");
   if (n_persons == 0) return OP_OK;
-  if (!poses) return body_invalid(who, "null poses");
-  if (!unit || !box || !state) return body_invalid(who, "null output");
+  if (!poses) return invalid(who, "null poses");
+  if (!unit || !box || !state) return invalid(who, "null output");
   BodyArgs a{};
-  const int rc = body_limbs(who, a.limb);
-  if (rc) return rc;
-  int ndev = 0;
-  OP_HIP_CHECK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev || device >= kBodyMaxDevices) return body_invalid(who, "no HIP device " + std::to_string(device));
-  OP_HIP_CHECK(hipSetDevice(device));
+  RC(body_limbs(who, a.limb));
+  RC(use_device(who, device));
   const BodyBlock blk(0, n_persons);
   const size_t in_bytes = (size_t)n_persons * kPose * 8;
-  void *d_in = nullptr, *d_out = nullptr;
-  hipEvent_t ev[2] = {};
   std::vector<char> host(blk.bytes);
-  int res = OP_OK;
-  auto fail = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess || res) return;
-    set_error(std::string("op_body_rois: ") + what + ": " + hipGetErrorString(e));
-    res = OP_ERR_HIP;
-  };
-  fail(hipMalloc(&d_in, in_bytes), "hipMalloc");
-  if (!res) fail(hipMalloc(&d_out, blk.bytes), "hipMalloc");
-  for (int i = 0; i < 2 && !res; ++i) fail(hipEventCreate(&ev[i]), "hipEventCreate");
-  if (!res) fail(hipEventRecord(ev[0], nullptr), "hipEventRecord");
-  if (!res) fail(hipMemcpy(d_in, poses, in_bytes, hipMemcpyHostToDevice), "upload");
-  if (!res) {
-    a.poses = (const double*)d_in;
-    a.hdr = nullptr;
-    a.frame_stride = 0;
-    a.n_frames = 1;
-    a.cap = n_persons;
-    a.rows = n_persons;
-    blk.point(&a, (char*)d_out);
-    hipLaunchKernelGGL(body_rois_kernel, dim3((unsigned)((n_persons + kBodyThreads - 1) / kBodyThreads)),
-                       dim3(kBodyThreads), 0, nullptr, a);
-    fail(hipGetLastError(), "body_rois_kernel");
-  }
-  if (!res) fail(hipEventRecord(ev[1], nullptr), "hipEventRecord");
-  if (!res) fail(hipMemcpy(host.data(), d_out, blk.bytes, hipMemcpyDeviceToHost), "download");
-  if (!res) fail(hipDeviceSynchronize(), "kernel");
-  float ms = 0.0f;
-  if (!res) fail(hipEventElapsedTime(&ms, ev[0], ev[1]), "hipEventElapsedTime");
-  if (d_in) (void)hipFree(d_in);
-  if (d_out) (void)hipFree(d_out);
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  if (res) return res;
+  Job job(who, nullptr);
+  a.poses = (const double*)job.alloc(in_bytes);
+  char* d_out = (char*)job.alloc(blk.bytes);
+  job.begin();
+  job.upload((void*)a.poses, poses, in_bytes);
+  a.n_frames = 1;
+  a.cap = a.rows = n_persons;
+  body_run(job, a, blk, d_out, host);
+  if (job.finish("kernel")) return job.status();
   memcpy(unit, host.data() + blk.unit_at, (size_t)n_persons * 8);
   memcpy(box, host.data() + blk.box_at, (size_t)n_persons * 12 * 4);
   memcpy(state, host.data() + blk.state_at, (size_t)n_persons * 3 * 4);
-  body_done(device, ms);
+  g_body_last.done(device, job.ms());
   return OP_OK;
 }
 
 extern "C" int op_body_rois_staged(op_ctx* c, int32_t first, int32_t n, int32_t cap, int32_t* count,
                                    int32_t* frame_status, double* unit, int32_t* box, int32_t* state) {
   const char* who = "op_body_rois_staged";
-  if (!c) return body_invalid(who, "null context");
-  if (!count || !frame_status || !unit || !box || !state) return body_invalid(who, "null output");
-  if (n < 1 || cap < 1 || (int64_t)n * cap > kBodyMaxRows) return body_invalid(who, "n, cap: n >= 1, cap >= 1 and n * cap <= 16777216");
-  if (c->st_n < 1) {
-    set_error("op_body_rois_staged: no staged frames");
-    return OP_ERR_STATE;
-  }
-  if (first < 0 || first > c->st_n - n)
-    return body_invalid(who, "first, n: frames " + std::to_string(first) + " .. " + std::to_string((int64_t)first + n - 1) +
-                                 " are outside the " + std::to_string(c->st_n) + " staged frames");
+  if (!c) return invalid(who, "null context");
+  if (!count || !frame_status || !unit || !box || !state) return invalid(who, "null output");
+  if (n < 1 || cap < 1 || (int64_t)n * cap > kBodyMaxRows) return invalid(who, "n, cap: n >= 1, cap >= 1 and n * cap <= 16777216");
+  RC(staged_range(c, who, first, n));
   if (!c->pb.res_hdr || !c->pb.res_poses || c->pn < first + n) {
     set_error("op_body_rois_staged: no results of the staged frames (run op_run_staged first)");
     return OP_ERR_STATE;
   }
   BodyArgs a{};
-  int rc = body_limbs(who, a.limb);
-  if (rc) return rc;
+  RC(body_limbs(who, a.limb));
   RC(check_ctx(c, false));
   const int64_t rows = (int64_t)n * cap;
   const BodyBlock blk(n, rows);
-  void* d_out = nullptr;
-  hipEvent_t ev[2] = {};
   std::vector<char> host(blk.bytes);
-  int res = OP_OK;
-  auto fail = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess || res) return;
-    set_error(std::string("op_body_rois_staged: ") + what + ": " + hipGetErrorString(e));
-    res = OP_ERR_HIP;
-  };
-  fail(hipMalloc(&d_out, blk.bytes), "hipMalloc");
-  for (int i = 0; i < 2 && !res; ++i) fail(hipEventCreate(&ev[i]), "hipEventCreate");
   // ordered on the context stream, behind a queued run; the result rows are read where they lie
-  if (!res) fail(hipEventRecord(ev[0], c->stream), "hipEventRecord");
-  if (!res) {
-    a.poses = c->pb.res_poses + (size_t)first * c->pb.maxs * kPose;
-    a.hdr = c->pb.res_hdr + 4 * (size_t)first;
-    a.frame_stride = (int64_t)c->pb.maxs * kPose;
-    a.n_frames = n;
-    a.cap = cap;
-    a.rows = c->pb.maxs;
-    blk.point(&a, (char*)d_out);
-    hipLaunchKernelGGL(body_rois_kernel, dim3((unsigned)((rows + kBodyThreads - 1) / kBodyThreads)), dim3(kBodyThreads),
-                       0, c->stream, a);
-    fail(hipGetLastError(), "body_rois_kernel");
-  }
-  if (!res) fail(hipEventRecord(ev[1], c->stream), "hipEventRecord");
-  if (!res) fail(hipMemcpyAsync(host.data(), d_out, blk.bytes, hipMemcpyDeviceToHost, c->stream), "download");
-  // also after a failure: the buffers must outlive what was queued
-  fail(hipStreamSynchronize(c->stream), "kernel");
-  float ms = 0.0f;
-  if (!res) fail(hipEventElapsedTime(&ms, ev[0], ev[1]), "hipEventElapsedTime");
-  if (d_out) (void)hipFree(d_out);
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  if (res) return res;
+  Job job(who, c->stream);
+  char* d_out = (char*)job.alloc(blk.bytes);
+  job.begin();
+  a.poses = c->pb.res_poses + (size_t)first * c->pb.maxs * kPose;
+  a.hdr = c->pb.res_hdr + 4 * (size_t)first;
+  a.frame_stride = (int64_t)c->pb.maxs * kPose;
+  a.n_frames = n;
+  a.cap = cap;
+  a.rows = c->pb.maxs;
+  body_run(job, a, blk, d_out, host);
+  if (job.finish("kernel")) return job.status();
   memcpy(count, host.data() + blk.count_at, (size_t)n * 4);
   memcpy(frame_status, host.data() + blk.count_at + (size_t)n * 4, (size_t)n * 4);
   memcpy(unit, host.data() + blk.unit_at, (size_t)rows * 8);
   memcpy(box, host.data() + blk.box_at, (size_t)rows * 12 * 4);
   memcpy(state, host.data() + blk.state_at, (size_t)rows * 3 * 4);
-  body_done(c->device, ms);
+  g_body_last.done(c->device, job.ms());
   int most = 0;
   for (int i = 0; i < n; ++i) most = std::max(most, count[i]);
   if (most > cap) {  // the caller's rows are too few: count says how many are needed
@@ -342,13 +282,5 @@ extern "C" int op_body_rois_staged(op_ctx* c, int32_t first, int32_t n, int32_t 
 }
 
 extern "C" int op_body_last_ms(int32_t device, double* ms) {
-  if (!ms) return body_invalid("op_body_last_ms", "null ms");
-  if (device < 0 || device >= kBodyMaxDevices) return body_invalid("op_body_last_ms", "bad device " + std::to_string(device));
-  std::lock_guard<std::mutex> lock(g_body_mutex);
-  if (!g_body_ran[device]) {
-    set_error("op_body_last_ms: no op_body_rois or op_body_rois_staged has completed on device " + std::to_string(device));
-    return OP_ERR_STATE;
-  }
-  *ms = g_body_ms[device];
-  return OP_OK;
+  return g_body_last.get("op_body_last_ms", "op_body_rois or op_body_rois_staged", device, ms);
 }

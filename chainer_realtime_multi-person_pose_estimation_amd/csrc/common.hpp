@@ -13,6 +13,14 @@ namespace op {
 
 // Thread-local last error text for op_last_error().
 void set_error(const std::string& msg);
+// "<who>: <msg>" as the last error; OP_ERR_INVALID
+#pragma GCC visibility push(hidden)
+inline int invalid(const char* who, const std::string& msg) {
+  set_error(std::string(who) + ": " + msg);
+  return OP_ERR_INVALID;
+}
+inline int64_t pad16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+#pragma GCC visibility pop
 
 // OP_DEBUG_SYNC=1: synchronise after every kernel launch (outside graph capture) and report the
 // kernel a fault happened in.

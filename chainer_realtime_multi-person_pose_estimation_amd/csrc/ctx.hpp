@@ -257,6 +257,8 @@ int stage_maps_dev(op_ctx* c, const float* maps, int n, int lh, int lw, float** 
 int take_upload(op_ctx* c);
 void staged_sizes(op_ctx* c, int* in_w, int* in_h, int* map_w, int* map_h);
 int upload_one_frame(op_ctx* c, const uint8_t* bgr, int h, int w, int64_t row_stride);
+// "no staged frames" (OP_ERR_STATE), or frames first .. first + n - 1 (n >= 1) outside them
+int staged_range(op_ctx* c, const char* who, int32_t first, int32_t n);
 #pragma GCC visibility pop
 
 // Record an event pair around `fn`'s launches when profiling is on.

@@ -20,12 +20,12 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "common.hpp"
 #include "ctx.hpp"
+#include "oneshot.hpp"
 
 namespace op {
 namespace {
@@ -33,7 +33,6 @@ namespace {
 constexpr int kDrawMaxSide = 16384;
 constexpr double kDrawMaxCoord = 32768.0;
 constexpr int kDrawMaxRadius = 1024;
-constexpr int kDrawMaxDevices = 64;
 constexpr int kDrawThreads = 256;
 constexpr int kDrawChunk = kDrawThreads;  // primitives per pass: one per lane
 constexpr int kDrawTileW = 64, kDrawTileH = 16, kDrawRows = kDrawTileH / (kDrawThreads / kDrawTileW);
@@ -214,23 +213,18 @@ struct DrawHost {
   int64_t tiles = 0;
 };
 
-int draw_invalid(const char* who, const std::string& msg) {
-  set_error(std::string(who) + ": " + msg);
-  return OP_ERR_INVALID;
-}
-
 // Validates the lists of n frames (frame f is hw[2f] x hw[2f + 1]) and lays the records out; makes
 // no HIP call.
 int draw_pack(const char* who, int32_t n, const int32_t* hw, const int32_t* prim_offsets, const op_draw_prim* prims,
               DrawHost* out) {
-  if (!prim_offsets) return draw_invalid(who, "null prim_offsets");
+  if (!prim_offsets) return invalid(who, "null prim_offsets");
   int64_t prev = 0;
   for (int f = 0; f <= n; ++f) {
     if ((f == 0 && prim_offsets[f] != 0) || prim_offsets[f] < prev)
-      return draw_invalid(who, "prim_offsets: entry " + std::to_string(f) + " must start at 0 and never decrease");
+      return invalid(who, "prim_offsets: entry " + std::to_string(f) + " must start at 0 and never decrease");
     prev = prim_offsets[f];
   }
-  if (prim_offsets[n] > 0 && !prims) return draw_invalid(who, "null prims");
+  if (prim_offsets[n] > 0 && !prims) return invalid(who, "null prims");
   auto coord = [](double v) { return std::isfinite(v) && std::fabs(v) <= kDrawMaxCoord; };
   out->frames.resize(n);
   out->recs.reserve((size_t)prim_offsets[n]);
@@ -248,9 +242,9 @@ int draw_pack(const char* who, int32_t n, const int32_t* hw, const int32_t* prim
       DrawBox b;
       memset(&r, 0, sizeof(r));
       if (p.kind == OP_DRAW_BLEND) {
-        if (fr.pb >= 0) return draw_invalid(who, at + "kind: more than one BLEND in the list of frame " + std::to_string(f));
+        if (fr.pb >= 0) return invalid(who, at + "kind: more than one BLEND in the list of frame " + std::to_string(f));
         if (!std::isfinite(p.wa) || !std::isfinite(p.wb) || !std::isfinite(p.gamma))
-          return draw_invalid(who, at + "wa, wb, gamma: a blend weight that is not finite");
+          return invalid(who, at + "wa, wb, gamma: a blend weight that is not finite");
         fr.pb = (int32_t)out->recs.size();
         fr.blend = 1;
         fr.wa = p.wa;
@@ -260,9 +254,9 @@ int draw_pack(const char* who, int32_t n, const int32_t* hw, const int32_t* prim
       }
       if (p.kind == OP_DRAW_LINE) {
         if (!coord(p.x0) || !coord(p.y0) || !coord(p.x1) || !coord(p.y1))
-          return draw_invalid(who, at + "x0, y0, x1, y1: a coordinate that is not finite or above 32768 in magnitude");
+          return invalid(who, at + "x0, y0, x1, y1: a coordinate that is not finite or above 32768 in magnitude");
         if (!(p.thickness > 0.0) || !(p.thickness <= kDrawMaxCoord))
-          return draw_invalid(who, at + "thickness must be in (0, 32768]");
+          return invalid(who, at + "thickness must be in (0, 32768]");
         const double rr = p.thickness / 2.0;
         r.x0 = p.x0;
         r.y0 = p.y0;
@@ -278,8 +272,8 @@ int draw_pack(const char* who, int32_t n, const int32_t* hw, const int32_t* prim
         r.col = 0u;
       } else if (p.kind == OP_DRAW_DISC) {
         if (!coord(p.x0) || !coord(p.y0) || p.x0 != std::floor(p.x0) || p.y0 != std::floor(p.y0))
-          return draw_invalid(who, at + "x0, y0: a disc centre that is not a whole number of at most 32768 in magnitude");
-        if (p.radius < 0 || p.radius > kDrawMaxRadius) return draw_invalid(who, at + "radius must be in 0 .. 1024");
+          return invalid(who, at + "x0, y0: a disc centre that is not a whole number of at most 32768 in magnitude");
+        if (p.radius < 0 || p.radius > kDrawMaxRadius) return invalid(who, at + "radius must be in 0 .. 1024");
         const int32_t cx = (int32_t)p.x0, cy = (int32_t)p.y0;
         b.lx = cx - p.radius;
         b.hx = cx + p.radius;
@@ -287,7 +281,7 @@ int draw_pack(const char* who, int32_t n, const int32_t* hw, const int32_t* prim
         b.hy = cy + p.radius;
         r.col = kDrawDiscBit;
       } else {
-        return draw_invalid(who, at + "unknown kind " + std::to_string(p.kind));
+        return invalid(who, at + "unknown kind " + std::to_string(p.kind));
       }
       r.col |= (uint32_t)p.bgr[0] | ((uint32_t)p.bgr[1] << 8) | ((uint32_t)p.bgr[2] << 16);
       out->boxes.push_back(b);
@@ -296,26 +290,37 @@ int draw_pack(const char* who, int32_t n, const int32_t* hw, const int32_t* prim
     fr.p1 = (int32_t)out->recs.size();
     if (fr.pb < 0) fr.pb = fr.p1;
     fr.tiles_x = (fr.w + kDrawTileW - 1) / kDrawTileW;
-    if (out->tiles > INT32_MAX) return draw_invalid(who, "more than 2^31 - 1 pixel tiles in the batch");
+    if (out->tiles > INT32_MAX) return invalid(who, "more than 2^31 - 1 pixel tiles in the batch");
     fr.tile0 = (int32_t)out->tiles;
     out->tiles += (int64_t)fr.tiles_x * ((fr.h + kDrawTileH - 1) / kDrawTileH);
   }
-  if (out->tiles > INT32_MAX) return draw_invalid(who, "more than 2^31 - 1 pixel tiles in the batch");
+  if (out->tiles > INT32_MAX) return invalid(who, "more than 2^31 - 1 pixel tiles in the batch");
   return OP_OK;
 }
 
-std::mutex g_draw_mutex;
-double g_draw_ms[kDrawMaxDevices];
-bool g_draw_ran[kDrawMaxDevices];
+LastMs g_draw_last;
 
-void draw_done(int device, float ms) {
-  if (device < 0 || device >= kDrawMaxDevices) return;
-  std::lock_guard<std::mutex> lock(g_draw_mutex);
-  g_draw_ms[device] = (double)ms;
-  g_draw_ran[device] = true;
+// The device tables of dh in the job's buffers
+DrawArgs draw_alloc(Job& job, const DrawHost& dh) {
+  DrawArgs a;
+  a.frames = (const DrawFrame*)job.alloc(dh.frames.size() * sizeof(DrawFrame));
+  a.boxes = (const DrawBox*)job.alloc(dh.boxes.size() * sizeof(DrawBox));
+  a.recs = (const DrawRec*)job.alloc(dh.recs.size() * sizeof(DrawRec));
+  a.n = (int32_t)dh.frames.size();
+  return a;
 }
 
-int64_t draw_pad16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+// Uploads dh (its frames' src / dst set) and queues draw_tiles; ends the job's timing
+void draw_run(Job& job, const DrawHost& dh, const DrawArgs& a) {
+  job.upload((void*)a.frames, dh.frames.data(), dh.frames.size() * sizeof(DrawFrame));
+  job.upload((void*)a.boxes, dh.boxes.data(), dh.boxes.size() * sizeof(DrawBox));
+  job.upload((void*)a.recs, dh.recs.data(), dh.recs.size() * sizeof(DrawRec));
+  if (job.ok()) {
+    hipLaunchKernelGGL(draw_tiles, dim3((unsigned)dh.tiles), dim3(kDrawThreads), 0, job.stream(), a);
+    job.check(hipGetLastError(), "draw_tiles");
+  }
+  job.end();
+}
 
 }  // namespace
 }  // namespace op
@@ -326,157 +331,69 @@ extern "C" int op_draw(int32_t device, int32_t n, const uint8_t* const* bgr, con
                        const int32_t* hw, const int32_t* prim_offsets, const op_draw_prim* prims,
                        uint8_t* const* out) {
   const char* who = "op_draw";
-  if (n < 1 || n > (1 << 20)) return draw_invalid(who, "n must be in 1 .. 1048576");
-  if (!bgr) return draw_invalid(who, "null bgr");
-  if (!row_stride) return draw_invalid(who, "null row_stride");
-  if (!hw) return draw_invalid(who, "null hw");
-  if (!out) return draw_invalid(who, "null out");
-  for (int f = 0; f < n; ++f) {
-    const std::string at = "frame " + std::to_string(f);
-    if (hw[2 * f] < 1 || hw[2 * f] > kDrawMaxSide || hw[2 * f + 1] < 1 || hw[2 * f + 1] > kDrawMaxSide)
-      return draw_invalid(who, "hw: " + at + ": h, w must be in 1 .. 16384");
-    if (!bgr[f]) return draw_invalid(who, "bgr: " + at + ": null image");
-    if (!out[f]) return draw_invalid(who, "out: " + at + ": null image");
-    if (row_stride[f] < (int64_t)hw[2 * f + 1] * 3)
-      return draw_invalid(who, "row_stride: " + at + ": fewer than 3 w bytes per row");
-  }
+  if (n < 1 || n > (1 << 20)) return invalid(who, "n must be in 1 .. 1048576");
+  RC(check_frames(who, n, bgr, row_stride, hw, out));
   DrawHost dh;
-  const int rc = draw_pack(who, n, hw, prim_offsets, prims, &dh);
-  if (rc) return rc;
-  int ndev = 0;
-  OP_HIP_CHECK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev || device >= kDrawMaxDevices) return draw_invalid(who, "no HIP device " + std::to_string(device));
-  OP_HIP_CHECK(hipSetDevice(device));
+  RC(draw_pack(who, n, hw, prim_offsets, prims, &dh));
+  RC(use_device(who, device));
   std::vector<int64_t> off(n + 1, 0);  // source and destination frames share one layout: rows of 3 w bytes
-  for (int f = 0; f < n; ++f) off[f + 1] = off[f] + draw_pad16((int64_t)dh.frames[f].h * dh.frames[f].w * 3);
-  enum { FRAMES, BOXES, RECS, SRC, DST, NBUF };
-  const size_t sizes[NBUF] = {dh.frames.size() * sizeof(DrawFrame), dh.boxes.size() * sizeof(DrawBox),
-                              dh.recs.size() * sizeof(DrawRec), (size_t)off[n], (size_t)off[n]};
-  void* d[NBUF] = {};
-  hipEvent_t ev[2] = {};
-  int res = OP_OK;
-  auto fail = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess || res) return;
-    set_error(std::string("op_draw: ") + what + ": " + hipGetErrorString(e));
-    res = OP_ERR_HIP;
-  };
-  for (int i = 0; i < NBUF && !res; ++i)
-    if (sizes[i]) fail(hipMalloc(&d[i], sizes[i]), "hipMalloc");
-  for (int i = 0; i < 2 && !res; ++i) fail(hipEventCreate(&ev[i]), "hipEventCreate");
-  if (!res) fail(hipEventRecord(ev[0], nullptr), "hipEventRecord");
-  for (int f = 0; f < n && !res; ++f) {
+  for (int f = 0; f < n; ++f) off[f + 1] = off[f] + pad16((int64_t)dh.frames[f].h * dh.frames[f].w * 3);
+  Job job(who, nullptr);
+  const DrawArgs a = draw_alloc(job, dh);
+  uint8_t* src = (uint8_t*)job.alloc((size_t)off[n]);
+  uint8_t* dst = (uint8_t*)job.alloc((size_t)off[n]);
+  job.begin();
+  for (int f = 0; f < n && job.ok(); ++f) {
     DrawFrame& fr = dh.frames[f];
-    fr.src = (const uint8_t*)d[SRC] + off[f];
-    fr.dst = (uint8_t*)d[DST] + off[f];
+    fr.src = src + off[f];
+    fr.dst = dst + off[f];
     fr.src_stride = (int64_t)fr.w * 3;
-    fail(hipMemcpy2D((void*)fr.src, (size_t)fr.w * 3, bgr[f], (size_t)row_stride[f], (size_t)fr.w * 3, (size_t)fr.h,
-                     hipMemcpyHostToDevice),
-         "frame upload");
+    job.upload2d((void*)fr.src, (size_t)fr.w * 3, bgr[f], (size_t)row_stride[f], (size_t)fr.w * 3, (size_t)fr.h,
+                 "frame upload");
   }
-  if (!res) fail(hipMemcpy(d[FRAMES], dh.frames.data(), sizes[FRAMES], hipMemcpyHostToDevice), "upload");
-  if (!res && sizes[BOXES]) fail(hipMemcpy(d[BOXES], dh.boxes.data(), sizes[BOXES], hipMemcpyHostToDevice), "upload");
-  if (!res && sizes[RECS]) fail(hipMemcpy(d[RECS], dh.recs.data(), sizes[RECS], hipMemcpyHostToDevice), "upload");
-  if (!res) {
-    DrawArgs a;
-    a.frames = (const DrawFrame*)d[FRAMES];
-    a.boxes = (const DrawBox*)d[BOXES];
-    a.recs = (const DrawRec*)d[RECS];
-    a.n = n;
-    hipLaunchKernelGGL(draw_tiles, dim3((unsigned)dh.tiles), dim3(kDrawThreads), 0, nullptr, a);
-    fail(hipGetLastError(), "draw_tiles");
-  }
-  if (!res) fail(hipEventRecord(ev[1], nullptr), "hipEventRecord");
-  if (!res) fail(hipDeviceSynchronize(), "kernel");
-  float ms = 0.0f;
-  if (!res) fail(hipEventElapsedTime(&ms, ev[0], ev[1]), "hipEventElapsedTime");
-  for (int f = 0; f < n && !res; ++f)
-    fail(hipMemcpy(out[f], dh.frames[f].dst, (size_t)dh.frames[f].h * dh.frames[f].w * 3, hipMemcpyDeviceToHost),
-         "download");
-  for (void* p : d)
-    if (p) (void)hipFree(p);
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  if (!res) draw_done(device, ms);
-  return res;
+  draw_run(job, dh, a);
+  job.finish("kernel");
+  for (int f = 0; f < n; ++f) job.download(out[f], dh.frames[f].dst, (size_t)dh.frames[f].h * dh.frames[f].w * 3);
+  if (job.ok()) g_draw_last.done(device, job.ms());
+  return job.status();
 }
 
 extern "C" int op_draw_staged(op_ctx* c, int32_t first, int32_t n, const int32_t* prim_offsets,
                               const op_draw_prim* prims, uint8_t* out) {
   const char* who = "op_draw_staged";
-  if (!c) return draw_invalid(who, "null context");
-  if (n < 1 || n > (1 << 20)) return draw_invalid(who, "n must be in 1 .. 1048576");
-  if (!out) return draw_invalid(who, "null out");
-  if (c->st_n < 1) {
-    set_error("op_draw_staged: no staged frames");
-    return OP_ERR_STATE;
-  }
-  if (first < 0 || first > c->st_n - n)
-    return draw_invalid(who, "first, n: frames " + std::to_string(first) + " .. " + std::to_string((int64_t)first + n - 1) +
-                                 " are outside the " + std::to_string(c->st_n) + " staged frames");
-  if (c->st_h > kDrawMaxSide || c->st_w > kDrawMaxSide) return draw_invalid(who, "staged frames above 16384 in h or w");
+  if (!c) return invalid(who, "null context");
+  if (n < 1 || n > (1 << 20)) return invalid(who, "n must be in 1 .. 1048576");
+  if (!out) return invalid(who, "null out");
+  RC(staged_range(c, who, first, n));
+  if (c->st_h > kDrawMaxSide || c->st_w > kDrawMaxSide) return invalid(who, "staged frames above 16384 in h or w");
   std::vector<int32_t> hw((size_t)n * 2);
   for (int f = 0; f < n; ++f) {
     hw[2 * f] = c->st_h;
     hw[2 * f + 1] = c->st_w;
   }
   DrawHost dh;
-  int rc = draw_pack(who, n, hw.data(), prim_offsets, prims, &dh);
-  if (rc) return rc;
+  RC(draw_pack(who, n, hw.data(), prim_offsets, prims, &dh));
   RC(check_ctx(c, false));
   const size_t fbytes = (size_t)c->st_h * c->st_w * 3;
-  enum { FRAMES, BOXES, RECS, DST, NBUF };
-  const size_t sizes[NBUF] = {dh.frames.size() * sizeof(DrawFrame), dh.boxes.size() * sizeof(DrawBox),
-                              dh.recs.size() * sizeof(DrawRec), fbytes * n};
-  void* d[NBUF] = {};
-  hipEvent_t ev[2] = {};
-  int res = OP_OK;
-  auto fail = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess || res) return;
-    set_error(std::string("op_draw_staged: ") + what + ": " + hipGetErrorString(e));
-    res = OP_ERR_HIP;
-  };
-  for (int i = 0; i < NBUF && !res; ++i)
-    if (sizes[i]) fail(hipMalloc(&d[i], sizes[i]), "hipMalloc");
-  for (int i = 0; i < 2 && !res; ++i) fail(hipEventCreate(&ev[i]), "hipEventCreate");
-  for (int f = 0; f < n && !res; ++f) {
+  Job job(who, c->stream);  // everything is ordered on the context stream, behind a queued run
+  const DrawArgs a = draw_alloc(job, dh);
+  uint8_t* dst = (uint8_t*)job.alloc(fbytes * n);
+  for (int f = 0; f < n && job.ok(); ++f) {
     DrawFrame& fr = dh.frames[f];
     fr.src = c->d_frames + (size_t)(first + f) * fbytes;  // read in place
-    fr.dst = (uint8_t*)d[DST] + (size_t)f * fbytes;
+    fr.dst = dst + (size_t)f * fbytes;
     fr.src_stride = (int64_t)c->st_w * 3;
   }
-  // everything below is ordered on the context stream, behind a queued run
-  if (!res) fail(hipEventRecord(ev[0], c->stream), "hipEventRecord");
-  if (!res) fail(hipMemcpyAsync(d[FRAMES], dh.frames.data(), sizes[FRAMES], hipMemcpyHostToDevice, c->stream), "upload");
-  if (!res && sizes[BOXES])
-    fail(hipMemcpyAsync(d[BOXES], dh.boxes.data(), sizes[BOXES], hipMemcpyHostToDevice, c->stream), "upload");
-  if (!res && sizes[RECS])
-    fail(hipMemcpyAsync(d[RECS], dh.recs.data(), sizes[RECS], hipMemcpyHostToDevice, c->stream), "upload");
-  if (!res) {
-    DrawArgs a;
-    a.frames = (const DrawFrame*)d[FRAMES];
-    a.boxes = (const DrawBox*)d[BOXES];
-    a.recs = (const DrawRec*)d[RECS];
-    a.n = n;
-    hipLaunchKernelGGL(draw_tiles, dim3((unsigned)dh.tiles), dim3(kDrawThreads), 0, c->stream, a);
-    fail(hipGetLastError(), "draw_tiles");
-  }
-  if (!res) fail(hipEventRecord(ev[1], c->stream), "hipEventRecord");
-  if (!res) fail(hipMemcpyAsync(out, d[DST], sizes[DST], hipMemcpyDeviceToHost, c->stream), "download");
-  // also after a failure: dh's vectors and the buffers must outlive what was queued
-  fail(hipStreamSynchronize(c->stream), "kernel");
-  float ms = 0.0f;
-  if (!res) fail(hipEventElapsedTime(&ms, ev[0], ev[1]), "hipEventElapsedTime");
-  for (void* p : d)
-    if (p) (void)hipFree(p);
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  if (!res) draw_done(c->device, ms);
-  return res;
+  job.begin();
+  draw_run(job, dh, a);
+  job.download(out, dst, fbytes * n);
+  if (job.finish("kernel") == OP_OK) g_draw_last.done(c->device, job.ms());
+  return job.status();
 }
 
 extern "C" int op_staged_info(op_ctx* c, int32_t* n, int32_t* h, int32_t* w) {
-  if (!c) return draw_invalid("op_staged_info", "null context");
-  if (!n || !h || !w) return draw_invalid("op_staged_info", "null output");
+  if (!c) return invalid("op_staged_info", "null context");
+  if (!n || !h || !w) return invalid("op_staged_info", "null output");
   const bool any = c->st_n > 0;
   *n = any ? c->st_n : 0;
   *h = any ? c->st_h : 0;
@@ -485,13 +402,5 @@ extern "C" int op_staged_info(op_ctx* c, int32_t* n, int32_t* h, int32_t* w) {
 }
 
 extern "C" int op_draw_last_ms(int32_t device, double* ms) {
-  if (!ms) return draw_invalid("op_draw_last_ms", "null ms");
-  if (device < 0 || device >= kDrawMaxDevices) return draw_invalid("op_draw_last_ms", "bad device " + std::to_string(device));
-  std::lock_guard<std::mutex> lock(g_draw_mutex);
-  if (!g_draw_ran[device]) {
-    set_error("op_draw_last_ms: no op_draw or op_draw_staged has completed on device " + std::to_string(device));
-    return OP_ERR_STATE;
-  }
-  *ms = g_draw_ms[device];
-  return OP_OK;
+  return g_draw_last.get("op_draw_last_ms", "op_draw or op_draw_staged", device, ms);
 }

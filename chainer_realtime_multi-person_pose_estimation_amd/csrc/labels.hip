@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "oneshot.hpp"
 
 namespace op {
 namespace {
@@ -218,30 +219,25 @@ void axis_tap_host(int o, int L, int oL, double* out) {
   out[2] = u - (double)i0;
 }
 
-int lab_invalid(const char* who, const std::string& msg) {
-  set_error(std::string(who) + ": " + msg);
-  return OP_ERR_INVALID;
-}
-
 }  // namespace
 
 int labels_pack(const char* who, int32_t n, int32_t h, int32_t w, int32_t downscale, const double* poses,
                 const int32_t* pose_offsets, double heatmap_sigma, double paf_width, LabelHost* out) {
   if (n < 1 || n > 65535 || h < 1 || w < 1 || h > 16384 || w > 16384)
-    return lab_invalid(who, "bad shape (1 <= n <= 65535, 1 <= h, w <= 16384)");
+    return invalid(who, "bad shape (1 <= n <= 65535, 1 <= h, w <= 16384)");
   if (downscale < 1 || (downscale > 1 && (h % downscale || w % downscale || h / downscale < 2 || w / downscale < 2)))
-    return lab_invalid(who, "bad downscale (1, or a divisor of h and w with h/downscale, w/downscale >= 2)");
-  if (!(heatmap_sigma > 0.0) || !std::isfinite(heatmap_sigma)) return lab_invalid(who, "heatmap_sigma must be > 0");
-  if (!(paf_width >= 0.0) || !std::isfinite(paf_width)) return lab_invalid(who, "paf_width must be >= 0");
-  if (!pose_offsets) return lab_invalid(who, "null pose_offsets");
-  if (pose_offsets[0] != 0) return lab_invalid(who, "pose_offsets[0] must be 0");
+    return invalid(who, "bad downscale (1, or a divisor of h and w with h/downscale, w/downscale >= 2)");
+  if (!(heatmap_sigma > 0.0) || !std::isfinite(heatmap_sigma)) return invalid(who, "heatmap_sigma must be > 0");
+  if (!(paf_width >= 0.0) || !std::isfinite(paf_width)) return invalid(who, "paf_width must be >= 0");
+  if (!pose_offsets) return invalid(who, "null pose_offsets");
+  if (pose_offsets[0] != 0) return invalid(who, "pose_offsets[0] must be 0");
   for (int f = 0; f < n; ++f)
-    if (pose_offsets[f + 1] < pose_offsets[f]) return lab_invalid(who, "pose_offsets must not decrease");
+    if (pose_offsets[f + 1] < pose_offsets[f]) return invalid(who, "pose_offsets must not decrease");
   const int64_t total = pose_offsets[n];
-  if (total > (1 << 22)) return lab_invalid(who, "too many people (the record offsets are 32-bit)");
-  if (total > 0 && !poses) return lab_invalid(who, "null poses with a non-zero person count");
+  if (total > (1 << 22)) return invalid(who, "too many people (the record offsets are 32-bit)");
+  if (total > 0 && !poses) return invalid(who, "null poses with a non-zero person count");
   for (int64_t i = 0; i < total * OP_N_JOINTS * 3; ++i)
-    if (!std::isfinite(poses[i])) return lab_invalid(who, "non-finite pose value");
+    if (!std::isfinite(poses[i])) return invalid(who, "non-finite pose value");
 
   op_params prm;
   op_default_params(&prm);  // limbs_point
@@ -331,40 +327,31 @@ using namespace op;
 extern "C" int op_make_labels(int32_t device, int32_t n, int32_t h, int32_t w, int32_t downscale, const double* poses,
                               const int32_t* pose_offsets, const uint8_t* mask, double heatmap_sigma,
                               double paf_width, float* pafs, float* heatmaps, uint8_t* ignore) {
+  const char* who = "op_make_labels";
   LabelHost lh;
-  const int rc = labels_pack("op_make_labels", n, h, w, downscale, poses, pose_offsets, heatmap_sigma, paf_width, &lh);
+  int rc = labels_pack(who, n, h, w, downscale, poses, pose_offsets, heatmap_sigma, paf_width, &lh);
   if (rc) return rc;
-  int ndev = 0;
-  OP_HIP_CHECK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) {
-    set_error("op_make_labels: no HIP device " + std::to_string(device));
-    return OP_ERR_INVALID;
-  }
-  OP_HIP_CHECK(hipSetDevice(device));
-  const size_t plane = (size_t)lh.oh * lh.ow, mbytes = (size_t)n * h * w;
-  const size_t sizes[6] = {lh.rec.size() * sizeof(double), lh.idx.size() * sizeof(int32_t), mask ? mbytes : 0,
-                           pafs ? n * OP_N_PAF * plane * sizeof(float) : 0,
+  rc = use_device(who, device);
+  if (rc) return rc;
+  const size_t plane = (size_t)lh.oh * lh.ow;
+  const size_t sizes[3] = {pafs ? n * OP_N_PAF * plane * sizeof(float) : 0,
                            heatmaps ? n * OP_N_HEAT * plane * sizeof(float) : 0, ignore ? n * plane : 0};
-  void* d[6] = {};
-  int res = OP_OK;
-  auto fail = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess || res) return;
-    set_error(std::string("op_make_labels: ") + what + ": " + hipGetErrorString(e));
-    res = OP_ERR_HIP;
-  };
-  for (int i = 0; i < 6 && !res; ++i)
-    if (sizes[i]) fail(hipMalloc(&d[i], sizes[i]), "hipMalloc");
-  if (!res) fail(hipMemcpy(d[0], lh.rec.data(), sizes[0], hipMemcpyHostToDevice), "records upload");
-  if (!res) fail(hipMemcpy(d[1], lh.idx.data(), sizes[1], hipMemcpyHostToDevice), "index upload");
-  if (!res && mask) fail(hipMemcpy(d[2], mask, sizes[2], hipMemcpyHostToDevice), "mask upload");
-  if (!res)
-    res = launch_make_labels(lh, (const double*)d[0], (const int32_t*)d[1], (const uint8_t*)d[2], n, h, w, downscale,
-                             heatmap_sigma, paf_width, (float*)d[3], (float*)d[4], (uint8_t*)d[5], nullptr);
-  if (!res) fail(hipDeviceSynchronize(), "make_labels");
   void* host[3] = {pafs, heatmaps, ignore};
-  for (int i = 0; i < 3 && !res; ++i)
-    if (host[i]) fail(hipMemcpy(host[i], d[3 + i], sizes[3 + i], hipMemcpyDeviceToHost), "download");
-  for (void* p : d)
-    if (p) (void)hipFree(p);
-  return res;
+  Job job(who, nullptr);
+  double* d_rec = (double*)job.alloc(lh.rec.size() * sizeof(double));
+  int32_t* d_idx = (int32_t*)job.alloc(lh.idx.size() * sizeof(int32_t));
+  uint8_t* d_mask = (uint8_t*)job.alloc(mask ? (size_t)n * h * w : 0);
+  void* d_out[3];
+  for (int i = 0; i < 3; ++i) d_out[i] = job.alloc(sizes[i]);
+  job.upload(d_rec, lh.rec.data(), lh.rec.size() * sizeof(double), "records upload");
+  job.upload(d_idx, lh.idx.data(), lh.idx.size() * sizeof(int32_t), "index upload");
+  job.upload(d_mask, mask, mask ? (size_t)n * h * w : 0, "mask upload");
+  if (job.ok()) {
+    rc = launch_make_labels(lh, d_rec, d_idx, d_mask, n, h, w, downscale, heatmap_sigma, paf_width, (float*)d_out[0],
+                            (float*)d_out[1], (uint8_t*)d_out[2], nullptr);
+    if (rc) return rc;
+  }
+  job.finish("make_labels");
+  for (int i = 0; i < 3; ++i) job.download(host[i], d_out[i], sizes[i]);
+  return job.status();
 }

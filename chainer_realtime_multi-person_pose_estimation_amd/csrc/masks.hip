@@ -30,7 +30,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -43,7 +42,6 @@ namespace {
 constexpr int kMaskMaxSide = 16384;
 constexpr double kMaskMaxCoord = 65536.0;
 constexpr int kMaskUp = 5;  // rleFrPoly's upsampling
-constexpr int kMaskMaxDevices = 64;
 constexpr int kFillThreads = 256;
 constexpr int kFillWords = 2048;  // LDS words per bit array of a column block
 constexpr int kFillMaxCols = 64;
@@ -223,23 +221,16 @@ __global__ __launch_bounds__(kFillThreads) void mask_fill(MaskArgs a) {
   mask_store(miss, a.out_miss + im.out_off, im.h, im.w, b.c0, b.nc, Wb * 32, tid);
 }
 
-// ---- host ----
-int mask_invalid(const char* who, const std::string& msg) {
-  set_error(std::string(who) + ": " + msg);
-  return OP_ERR_INVALID;
-}
-
-int64_t pad16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 }  // namespace
 
+// ---- host ----
 int mask_offsets(const char* who, const char* name, const int64_t* o64, const int32_t* o32, int64_t count) {
-  if (!o64 && !o32) return mask_invalid(who, std::string("null ") + name);
+  if (!o64 && !o32) return invalid(who, std::string("null ") + name);
   int64_t prev = 0;
   for (int64_t i = 0; i <= count; ++i) {
     const int64_t v = o64 ? o64[i] : (int64_t)o32[i];
     if ((i == 0 && v != 0) || v < prev)
-      return mask_invalid(who, std::string(name) + ": entry " + std::to_string(i) + " must start at 0 and never decrease");
+      return invalid(who, std::string(name) + ": entry " + std::to_string(i) + " must start at 0 and never decrease");
     prev = v;
   }
   return OP_OK;
@@ -248,25 +239,25 @@ int mask_offsets(const char* who, const char* name, const int64_t* o64, const in
 int mask_pack(const char* who, int32_t n, const int32_t* hw, const int32_t* ann_offsets, const int32_t* ann_role,
               const int32_t* part_offsets, const int32_t* part_kind, const int64_t* data_offsets, const double* xy,
               const uint32_t* counts, uint8_t* const* out_ann, uint8_t* const* ann_frames, MaskHost* out) {
-  if (n < 1 || n > (1 << 20)) return mask_invalid(who, "n must be in 1 .. 1048576");
-  if (!hw) return mask_invalid(who, "null hw");
+  if (n < 1 || n > (1 << 20)) return invalid(who, "n must be in 1 .. 1048576");
+  if (!hw) return invalid(who, "null hw");
   for (int f = 0; f < n; ++f)
     if (hw[2 * f] < 1 || hw[2 * f] > kMaskMaxSide || hw[2 * f + 1] < 1 || hw[2 * f + 1] > kMaskMaxSide)
-      return mask_invalid(who, "hw: image " + std::to_string(f) + ": h, w must be in 1 .. 16384");
+      return invalid(who, "hw: image " + std::to_string(f) + ": h, w must be in 1 .. 16384");
   int rc = mask_offsets(who, "ann_offsets", nullptr, ann_offsets, n);
   if (rc) return rc;
   const int32_t A = ann_offsets[n];
-  if (A > 0 && !ann_role) return mask_invalid(who, "null ann_role");
+  if (A > 0 && !ann_role) return invalid(who, "null ann_role");
   for (int a = 0; a < A; ++a)
     if (ann_role[a] != OP_MASK_KEEP && ann_role[a] != OP_MASK_MISS && ann_role[a] != OP_MASK_CROWD)
-      return mask_invalid(who, "ann_role: annotation " + std::to_string(a) + ": unknown role " + std::to_string(ann_role[a]));
+      return invalid(who, "ann_role: annotation " + std::to_string(a) + ": unknown role " + std::to_string(ann_role[a]));
   rc = mask_offsets(who, "part_offsets", nullptr, part_offsets, A);
   if (rc) return rc;
   const int32_t P = part_offsets[A];
-  if (P > 0 && !part_kind) return mask_invalid(who, "null part_kind");
+  if (P > 0 && !part_kind) return invalid(who, "null part_kind");
   for (int p = 0; p < P; ++p)
     if (part_kind[p] != OP_MASK_POLYGON && part_kind[p] != OP_MASK_RLE)
-      return mask_invalid(who, "part_kind: part " + std::to_string(p) + ": unknown kind " + std::to_string(part_kind[p]));
+      return invalid(who, "part_kind: part " + std::to_string(p) + ": unknown kind " + std::to_string(part_kind[p]));
   rc = mask_offsets(who, "data_offsets", data_offsets, nullptr, P);
   if (rc) return rc;
   int64_t points = 0;
@@ -276,18 +267,18 @@ int mask_pack(const char* who, int32_t n, const int32_t* hw, const int32_t* ann_
       const int64_t lo = data_offsets[p], len = data_offsets[p + 1] - lo;
       const std::string at = "part " + std::to_string(p) + ": ";
       if (part_kind[p] == OP_MASK_POLYGON) {
-        if (!xy) return mask_invalid(who, "null xy");
+        if (!xy) return invalid(who, "null xy");
         if (len % 2 || len < 6)
-          return mask_invalid(who, "xy: " + at + "a polygon of " + std::to_string(len) + " numbers (an even count, at least 3 points)");
+          return invalid(who, "xy: " + at + "a polygon of " + std::to_string(len) + " numbers (an even count, at least 3 points)");
         for (int64_t i = 0; i < len; ++i)
           if (!std::isfinite(xy[lo + i]) || std::fabs(xy[lo + i]) > kMaskMaxCoord)
-            return mask_invalid(who, "xy: " + at + "a coordinate that is not finite or above 65536 in magnitude");
+            return invalid(who, "xy: " + at + "a coordinate that is not finite or above 65536 in magnitude");
       } else {
-        if (!counts) return mask_invalid(who, "null counts");
+        if (!counts) return invalid(who, "null counts");
         uint64_t sum = 0;
         for (int64_t i = 0; i < len; ++i) sum += counts[lo + i];
         if (sum != (uint64_t)pixels)
-          return mask_invalid(who, "counts: " + at + "the runs sum to " + std::to_string(sum) + ", the image has " +
+          return invalid(who, "counts: " + at + "the runs sum to " + std::to_string(sum) + ", the image has " +
                               std::to_string(pixels) + " pixels");
       }
     }
@@ -332,7 +323,7 @@ int mask_pack(const char* who, int32_t n, const int32_t* hw, const int32_t* ann_
           r.h = im.h;
           r.tw = tw;
           r.pad = 0;
-          if (len > INT32_MAX) return mask_invalid(who, "counts: part " + std::to_string(p) + ": too many runs");
+          if (len > INT32_MAX) return invalid(who, "counts: part " + std::to_string(p) + ": too many runs");
           out->counts.insert(out->counts.end(), counts + lo, counts + lo + len);
           out->rles.push_back(r);
           continue;
@@ -365,7 +356,7 @@ int mask_pack(const char* who, int32_t n, const int32_t* hw, const int32_t* ann_
           e.w = im.w;
           e.tw = tw;
           points += e.len;
-          if (points > INT32_MAX) return mask_invalid(who, "xy: more than 2^31 - 1 upsampled outline points in the batch");
+          if (points > INT32_MAX) return invalid(who, "xy: more than 2^31 - 1 upsampled outline points in the batch");
           out->edges.push_back(e);
           out->edge_start.push_back((int32_t)points);
         }
@@ -378,12 +369,7 @@ int mask_pack(const char* who, int32_t n, const int32_t* hw, const int32_t* ann_
   return OP_OK;
 }
 
-MaskDevice::~MaskDevice() {
-  for (void* p : d)
-    if (p) (void)hipFree(p);
-}
-
-hipError_t mask_launch(const MaskHost& mh, MaskDevice* md, hipEvent_t start, const char** what) {
+void mask_launch(Job& job, const MaskHost& mh, MaskDevice* md) {
   enum { IMAGES = MaskDevice::IMAGES, ANNS = MaskDevice::ANNS, PARTS = MaskDevice::PARTS, EDGES = MaskDevice::EDGES,
          ESTART = MaskDevice::ESTART, RLES = MaskDevice::RLES, COUNTS = MaskDevice::COUNTS, BLOCKS = MaskDevice::BLOCKS,
          PLANES = MaskDevice::PLANES, OALL = MaskDevice::OALL, OMISS = MaskDevice::OMISS, OANN = MaskDevice::OANN,
@@ -397,17 +383,12 @@ hipError_t mask_launch(const MaskHost& mh, MaskDevice* md, hipEvent_t start, con
                               (size_t)mh.plane_words * sizeof(uint32_t), (size_t)mh.out_bytes, (size_t)mh.out_bytes,
                               (size_t)mh.ann_bytes};
   void** d = md->d;
-  hipError_t e = hipSuccess;
-  *what = "hipMalloc";
+  for (int i = 0; i < NBUF; ++i) d[i] = job.alloc(sizes[i]);
+  job.begin();
   for (int i = 0; i < NBUF; ++i)
-    if (sizes[i] && (e = hipMalloc(&d[i], sizes[i])) != hipSuccess) return e;
-  *what = "hipEventRecord";
-  if (start && (e = hipEventRecord(start, nullptr)) != hipSuccess) return e;
-  *what = "upload";
-  for (int i = 0; i < NBUF; ++i)
-    if (host[i] && sizes[i] && (e = hipMemcpy(d[i], host[i], sizes[i], hipMemcpyHostToDevice)) != hipSuccess) return e;
-  *what = "hipMemset";
-  if (sizes[PLANES] && (e = hipMemset(d[PLANES], 0, sizes[PLANES])) != hipSuccess) return e;
+    if (host[i]) job.upload(d[i], host[i], sizes[i]);
+  job.memset(d[PLANES], 0, sizes[PLANES]);
+  if (!job.ok()) return;
   MaskArgs a;
   a.images = (const MaskImage*)d[IMAGES];
   a.anns = (const MaskAnn*)d[ANNS];
@@ -424,24 +405,21 @@ hipError_t mask_launch(const MaskHost& mh, MaskDevice* md, hipEvent_t start, con
   a.n_edges = (int32_t)mh.edges.size();
   a.total_points = mh.edge_start.back();
   if (a.total_points > 0) {
-    *what = "mask_toggles";
-    hipLaunchKernelGGL(mask_toggles, dim3((unsigned)(((int64_t)a.total_points + 255) / 256)), dim3(256), 0, nullptr, a);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(mask_toggles, dim3((unsigned)(((int64_t)a.total_points + 255) / 256)), dim3(256), 0,
+                       job.stream(), a);
+    job.check(hipGetLastError(), "mask_toggles");
   }
-  if (!mh.rles.empty()) {
-    *what = "mask_rle";
-    hipLaunchKernelGGL(mask_rle, dim3((unsigned)mh.rles.size()), dim3(256), 0, nullptr, a);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (!mh.rles.empty() && job.ok()) {
+    hipLaunchKernelGGL(mask_rle, dim3((unsigned)mh.rles.size()), dim3(256), 0, job.stream(), a);
+    job.check(hipGetLastError(), "mask_rle");
   }
-  *what = "mask_fill";
-  hipLaunchKernelGGL(mask_fill, dim3((unsigned)mh.blocks.size()), dim3(kFillThreads), 0, nullptr, a);
-  return hipGetLastError();
+  if (!job.ok()) return;
+  hipLaunchKernelGGL(mask_fill, dim3((unsigned)mh.blocks.size()), dim3(kFillThreads), 0, job.stream(), a);
+  job.check(hipGetLastError(), "mask_fill");
 }
 
 namespace {
-std::mutex g_mask_mutex;
-double g_mask_ms[kMaskMaxDevices];
-bool g_mask_ran[kMaskMaxDevices];
+LastMs g_mask_last;
 }  // namespace
 }  // namespace op
 
@@ -451,71 +429,31 @@ extern "C" int op_ignore_masks(int32_t device, int32_t n, const int32_t* hw, con
                                const int32_t* ann_role, const int32_t* part_offsets, const int32_t* part_kind,
                                const int64_t* data_offsets, const double* xy, const uint32_t* counts,
                                uint8_t* const* out_all, uint8_t* const* out_miss, uint8_t* const* out_ann) {
+  const char* who = "op_ignore_masks";
   MaskHost mh;
-  const int rc = mask_pack("op_ignore_masks", n, hw, ann_offsets, ann_role, part_offsets, part_kind, data_offsets, xy,
-                           counts, out_ann, nullptr, &mh);
+  const int rc = mask_pack(who, n, hw, ann_offsets, ann_role, part_offsets, part_kind, data_offsets, xy, counts, out_ann,
+                           nullptr, &mh);
   if (rc) return rc;
-  int ndev = 0;
-  OP_HIP_CHECK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev || device >= kMaskMaxDevices) {
-    set_error("op_ignore_masks: no HIP device " + std::to_string(device));
-    return OP_ERR_INVALID;
-  }
-  OP_HIP_CHECK(hipSetDevice(device));
+  const int rd = use_device(who, device);
+  if (rd) return rd;
+  Job job(who, nullptr);
   MaskDevice md;
-  hipEvent_t ev[2] = {};
-  int res = OP_OK;
-  auto fail = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess || res) return;
-    set_error(std::string("op_ignore_masks: ") + what + ": " + hipGetErrorString(e));
-    res = OP_ERR_HIP;
-  };
-  for (int i = 0; i < 2 && !res; ++i) fail(hipEventCreate(&ev[i]), "hipEventCreate");
-  if (!res) {
-    const char* what = "";
-    const hipError_t e = mask_launch(mh, &md, ev[0], &what);
-    fail(e, what);
-  }
-  if (!res) fail(hipEventRecord(ev[1], nullptr), "hipEventRecord");
-  if (!res) fail(hipDeviceSynchronize(), "kernels");
-  float ms = 0.0f;
-  if (!res) fail(hipEventElapsedTime(&ms, ev[0], ev[1]), "hipEventElapsedTime");
-  for (int f = 0; f < n && !res; ++f) {
+  mask_launch(job, mh, &md);
+  job.end();
+  job.finish("kernels");
+  for (int f = 0; f < n && job.ok(); ++f) {
     const MaskImage& im = mh.images[f];
     const size_t bytes = (size_t)im.h * im.w;
-    if (out_all && out_all[f])
-      fail(hipMemcpy(out_all[f], md.all() + im.out_off, bytes, hipMemcpyDeviceToHost), "mask_all download");
-    if (out_miss && out_miss[f])
-      fail(hipMemcpy(out_miss[f], md.miss() + im.out_off, bytes, hipMemcpyDeviceToHost), "mask_miss download");
-    for (int a = im.ann0; a < im.ann1 && !res; ++a)
+    if (out_all && out_all[f]) job.download(out_all[f], md.all() + im.out_off, bytes, "mask_all download");
+    if (out_miss && out_miss[f]) job.download(out_miss[f], md.miss() + im.out_off, bytes, "mask_miss download");
+    for (int a = im.ann0; a < im.ann1; ++a)
       if (mh.anns[a].out_off >= 0)
-        fail(hipMemcpy(out_ann[a], md.ann() + mh.anns[a].out_off, bytes, hipMemcpyDeviceToHost),
-             "annotation mask download");
+        job.download(out_ann[a], md.ann() + mh.anns[a].out_off, bytes, "annotation mask download");
   }
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  if (!res) {
-    std::lock_guard<std::mutex> lock(g_mask_mutex);
-    g_mask_ms[device] = (double)ms;
-    g_mask_ran[device] = true;
-  }
-  return res;
+  if (job.ok()) g_mask_last.done(device, job.ms());
+  return job.status();
 }
 
 extern "C" int op_ignore_masks_last_ms(int32_t device, double* ms) {
-  if (!ms) {
-    set_error("op_ignore_masks_last_ms: null ms");
-    return OP_ERR_INVALID;
-  }
-  if (device < 0 || device >= kMaskMaxDevices) {
-    set_error("op_ignore_masks_last_ms: bad device " + std::to_string(device));
-    return OP_ERR_INVALID;
-  }
-  std::lock_guard<std::mutex> lock(g_mask_mutex);
-  if (!g_mask_ran[device]) {
-    set_error("op_ignore_masks_last_ms: no op_ignore_masks has completed on device " + std::to_string(device));
-    return OP_ERR_STATE;
-  }
-  *ms = g_mask_ms[device];
-  return OP_OK;
+  return g_mask_last.get("op_ignore_masks_last_ms", "op_ignore_masks", device, ms);
 }

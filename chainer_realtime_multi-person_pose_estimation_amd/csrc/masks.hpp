@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "oneshot.hpp"
 
 namespace op {
 
@@ -47,17 +48,13 @@ struct MaskHost {
 
 // The batch on the device: the tables, the toggle planes and the row-major u8 masks (mask_all and
 // mask_miss of image f at all / miss + images[f].out_off, annotation a's own mask at
-// ann + anns[a].out_off where that is >= 0).  Frees its buffers when it goes.
+// ann + anns[a].out_off where that is >= 0), in buffers of the job that launched it.
 struct MaskDevice {
   enum { IMAGES, ANNS, PARTS, EDGES, ESTART, RLES, COUNTS, BLOCKS, PLANES, OALL, OMISS, OANN, NBUF };
   void* d[NBUF] = {};
   const uint8_t* all() const { return (const uint8_t*)d[OALL]; }
   const uint8_t* miss() const { return (const uint8_t*)d[OMISS]; }
   const uint8_t* ann() const { return (const uint8_t*)d[OANN]; }
-  MaskDevice() = default;
-  MaskDevice(const MaskDevice&) = delete;
-  MaskDevice& operator=(const MaskDevice&) = delete;
-  ~MaskDevice();
 };
 
 // "entry i must start at 0 and never decrease" for count + 1 offsets (one of o64 / o32); the message
@@ -71,9 +68,8 @@ int mask_pack(const char* who, int32_t n, const int32_t* hw, const int32_t* ann_
               const int32_t* part_offsets, const int32_t* part_kind, const int64_t* data_offsets, const double* xy,
               const uint32_t* counts, uint8_t* const* out_ann, uint8_t* const* ann_frames, MaskHost* out);
 
-// On the current device: allocates md's buffers, records `start` (if set) on the null stream,
-// uploads mh and queues mask_toggles, mask_rle and mask_fill there.  It does not wait.  On failure
-// *what names the step.
-hipError_t mask_launch(const MaskHost& mh, MaskDevice* md, hipEvent_t start, const char** what);
+// On the current device: allocates md's buffers from the job, begins its timing, uploads mh and
+// queues mask_toggles, mask_rle and mask_fill on its stream.  It does not wait; a failure is the job's.
+void mask_launch(Job& job, const MaskHost& mh, MaskDevice* md);
 
 }  // namespace op

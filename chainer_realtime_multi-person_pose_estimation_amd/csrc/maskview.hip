@@ -30,7 +30,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -41,7 +40,6 @@ namespace op {
 namespace {
 
 constexpr int kViewMaxCoord = 32768;
-constexpr int kViewMaxDevices = 64;
 constexpr int kViewThreads = 256;
 constexpr int kViewChunk = kViewThreads;  // discs per pass: one per lane
 constexpr int kViewTileW = 64, kViewTileH = 16, kViewPx = 4;  // 16 threads x 4 pixels per row, 16 rows
@@ -225,16 +223,7 @@ __global__ __launch_bounds__(kViewThreads) void view_tiles(ViewArgs a) {
 }
 
 // ---- host ----
-int view_invalid(const std::string& msg) {
-  set_error("op_annotation_views: " + msg);
-  return OP_ERR_INVALID;
-}
-
-int64_t view_pad16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
-std::mutex g_view_mutex;
-double g_view_ms[kViewMaxDevices];
-bool g_view_ran[kViewMaxDevices];
+LastMs g_view_last;
 
 }  // namespace
 }  // namespace op
@@ -248,9 +237,9 @@ extern "C" int op_annotation_views(int32_t device, int32_t n, const uint8_t* con
                                    const int32_t* kp_offsets, const int32_t* kp, uint8_t* const* out_ann,
                                    uint8_t* const* out_miss) {
   const char* who = "op_annotation_views";
-  if (n < 1 || n > (1 << 20)) return view_invalid("n must be in 1 .. 1048576");
-  if (!bgr) return view_invalid("null bgr");
-  if (!row_stride) return view_invalid("null row_stride");
+  if (n < 1 || n > (1 << 20)) return invalid(who, "n must be in 1 .. 1048576");
+  if (!bgr) return invalid(who, "null bgr");
+  if (!row_stride) return invalid(who, "null row_stride");
   MaskHost mh;
   int rc = mask_pack(who, n, hw, ann_offsets, ann_role, part_offsets, part_kind, data_offsets, xy, counts, nullptr,
                      out_ann, &mh);
@@ -263,28 +252,28 @@ extern "C" int op_annotation_views(int32_t device, int32_t n, const uint8_t* con
     memset(&fr, 0, sizeof(fr));
     fr.h = hw[2 * f];
     fr.w = hw[2 * f + 1];
-    if (!bgr[f]) return view_invalid("bgr: " + at + ": null image");
-    if (row_stride[f] < (int64_t)fr.w * 3) return view_invalid("row_stride: " + at + ": fewer than 3 w bytes per row");
+    if (!bgr[f]) return invalid(who, "bgr: " + at + ": null image");
+    if (row_stride[f] < (int64_t)fr.w * 3) return invalid(who, "row_stride: " + at + ": fewer than 3 w bytes per row");
     fr.ann0 = ann_offsets[f];
     fr.ann1 = ann_offsets[f + 1];
     fr.tiles_x = (fr.w + kViewTileW - 1) / kViewTileW;
     fr.tile0 = (int32_t)tiles;
     tiles += (int64_t)fr.tiles_x * ((fr.h + kViewTileH - 1) / kViewTileH);
-    if (tiles > INT32_MAX) return view_invalid("more than 2^31 - 1 pixel tiles in the batch");
+    if (tiles > INT32_MAX) return invalid(who, "more than 2^31 - 1 pixel tiles in the batch");
   }
   const int32_t A = ann_offsets[n];
-  if (A > 0 && !ann_tint) return view_invalid("null ann_tint");
+  if (A > 0 && !ann_tint) return invalid(who, "null ann_tint");
   for (int a = 0; a < A; ++a)
     if (ann_tint[a] != OP_VIEW_PERSON && ann_tint[a] != OP_VIEW_NO_KEYPOINTS && ann_tint[a] != OP_VIEW_CROWD)
-      return view_invalid("ann_tint: annotation " + std::to_string(a) + ": unknown tint " + std::to_string(ann_tint[a]));
+      return invalid(who, "ann_tint: annotation " + std::to_string(a) + ": unknown tint " + std::to_string(ann_tint[a]));
   rc = mask_offsets(who, "kp_offsets", nullptr, kp_offsets, A);
   if (rc) return rc;
   const int32_t K = kp_offsets[A];
-  if (K > 0 && !kp) return view_invalid("null kp");
+  if (K > 0 && !kp) return invalid(who, "null kp");
   for (int i = 0; i < K; ++i)
     for (int c = 0; c < 2; ++c)
       if (kp[3 * i + c] < -kViewMaxCoord || kp[3 * i + c] > kViewMaxCoord)
-        return view_invalid("kp: keypoint " + std::to_string(i) + ": a coordinate above 32768 in magnitude");
+        return invalid(who, "kp: keypoint " + std::to_string(i) + ": a coordinate above 32768 in magnitude");
   // everything is valid: the discs of the keypoints with v = 1 or 2, in order
   std::vector<ViewAnn> anns(A);
   std::vector<ViewDisc> discs;
@@ -300,98 +289,56 @@ extern "C" int op_annotation_views(int32_t device, int32_t n, const uint8_t* con
     }
     an.kp1 = (int32_t)discs.size();
   }
-  int ndev = 0;
-  OP_HIP_CHECK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev || device >= kViewMaxDevices) return view_invalid("no HIP device " + std::to_string(device));
-  OP_HIP_CHECK(hipSetDevice(device));
+  rc = use_device(who, device);
+  if (rc) return rc;
   std::vector<int64_t> off(n + 1, 0);  // source and destination frames share one layout: rows of 3 w bytes
   bool want_ann = false, want_miss = false;
   for (int f = 0; f < n; ++f) {
-    off[f + 1] = off[f] + view_pad16((int64_t)frames[f].h * frames[f].w * 3);
+    off[f + 1] = off[f] + pad16((int64_t)frames[f].h * frames[f].w * 3);
     want_ann = want_ann || (out_ann && out_ann[f]);
     want_miss = want_miss || (out_miss && out_miss[f]);
   }
-  enum { FRAMES, ANNS, DISCS, SRC, DANN, DMISS, NBUF };
-  const size_t sizes[NBUF] = {frames.size() * sizeof(ViewFrame), anns.size() * sizeof(ViewAnn),
-                              discs.size() * sizeof(ViewDisc), (size_t)off[n], want_ann ? (size_t)off[n] : 0,
-                              want_miss ? (size_t)off[n] : 0};
-  void* d[NBUF] = {};
+  Job job(who, nullptr);
+  ViewArgs a;
+  a.frames = (const ViewFrame*)job.alloc(frames.size() * sizeof(ViewFrame));
+  a.anns = (const ViewAnn*)job.alloc(anns.size() * sizeof(ViewAnn));
+  a.discs = (const ViewDisc*)job.alloc(discs.size() * sizeof(ViewDisc));
+  a.n = n;
+  uint8_t* src = (uint8_t*)job.alloc((size_t)off[n]);
+  uint8_t* dann = (uint8_t*)job.alloc(want_ann ? (size_t)off[n] : 0);
+  uint8_t* dmiss = (uint8_t*)job.alloc(want_miss ? (size_t)off[n] : 0);
   MaskDevice md;
-  hipEvent_t ev[2] = {};
-  int res = OP_OK;
-  auto fail = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess || res) return;
-    set_error(std::string("op_annotation_views: ") + what + ": " + hipGetErrorString(e));
-    res = OP_ERR_HIP;
-  };
-  for (int i = 0; i < NBUF && !res; ++i)
-    if (sizes[i]) fail(hipMalloc(&d[i], sizes[i]), "hipMalloc");
-  for (int i = 0; i < 2 && !res; ++i) fail(hipEventCreate(&ev[i]), "hipEventCreate");
-  if (!res) {  // the masks: masks.hip's kernels, queued on the null stream ahead of view_tiles
-    const char* what = "";
-    const hipError_t e = mask_launch(mh, &md, ev[0], &what);
-    fail(e, what);
-  }
-  for (int f = 0; f < n && !res; ++f) {
+  mask_launch(job, mh, &md);  // the masks: masks.hip's kernels, queued on the null stream ahead of view_tiles
+  for (int f = 0; f < n && job.ok(); ++f) {
     ViewFrame& fr = frames[f];
-    fr.src = (const uint8_t*)d[SRC] + off[f];
+    fr.src = src + off[f];
     fr.src_stride = (int64_t)fr.w * 3;
-    fr.dst_ann = out_ann && out_ann[f] ? (uint8_t*)d[DANN] + off[f] : nullptr;
-    fr.dst_miss = out_miss && out_miss[f] ? (uint8_t*)d[DMISS] + off[f] : nullptr;
+    fr.dst_ann = out_ann && out_ann[f] ? dann + off[f] : nullptr;
+    fr.dst_miss = out_miss && out_miss[f] ? dmiss + off[f] : nullptr;
     fr.miss = md.miss() + mh.images[f].out_off;
-    for (int a = fr.ann0; a < fr.ann1; ++a)  // out_off >= 0 wherever dst_ann is set
-      anns[a].mask = mh.anns[a].out_off >= 0 ? md.ann() + mh.anns[a].out_off : nullptr;
-    fail(hipMemcpy2D((void*)fr.src, (size_t)fr.w * 3, bgr[f], (size_t)row_stride[f], (size_t)fr.w * 3, (size_t)fr.h,
-                     hipMemcpyHostToDevice),
-         "frame upload");
+    for (int k = fr.ann0; k < fr.ann1; ++k)  // out_off >= 0 wherever dst_ann is set
+      anns[k].mask = mh.anns[k].out_off >= 0 ? md.ann() + mh.anns[k].out_off : nullptr;
+    job.upload2d((void*)fr.src, (size_t)fr.w * 3, bgr[f], (size_t)row_stride[f], (size_t)fr.w * 3, (size_t)fr.h,
+                 "frame upload");
   }
-  if (!res) fail(hipMemcpy(d[FRAMES], frames.data(), sizes[FRAMES], hipMemcpyHostToDevice), "upload");
-  if (!res && sizes[ANNS]) fail(hipMemcpy(d[ANNS], anns.data(), sizes[ANNS], hipMemcpyHostToDevice), "upload");
-  if (!res && sizes[DISCS]) fail(hipMemcpy(d[DISCS], discs.data(), sizes[DISCS], hipMemcpyHostToDevice), "upload");
-  if (!res) {
-    ViewArgs a;
-    a.frames = (const ViewFrame*)d[FRAMES];
-    a.anns = (const ViewAnn*)d[ANNS];
-    a.discs = (const ViewDisc*)d[DISCS];
-    a.n = n;
+  job.upload((void*)a.frames, frames.data(), frames.size() * sizeof(ViewFrame));
+  job.upload((void*)a.anns, anns.data(), anns.size() * sizeof(ViewAnn));
+  job.upload((void*)a.discs, discs.data(), discs.size() * sizeof(ViewDisc));
+  if (job.ok()) {
     hipLaunchKernelGGL(view_tiles, dim3((unsigned)tiles), dim3(kViewThreads), 0, nullptr, a);
-    fail(hipGetLastError(), "view_tiles");
+    job.check(hipGetLastError(), "view_tiles");
   }
-  if (!res) fail(hipEventRecord(ev[1], nullptr), "hipEventRecord");
-  if (!res) fail(hipDeviceSynchronize(), "kernels");
-  float ms = 0.0f;
-  if (!res) fail(hipEventElapsedTime(&ms, ev[0], ev[1]), "hipEventElapsedTime");
-  for (int f = 0; f < n && !res; ++f) {
+  job.end();
+  job.finish("kernels");
+  for (int f = 0; f < n; ++f) {
     const size_t bytes = (size_t)frames[f].h * frames[f].w * 3;
-    if (frames[f].dst_ann) fail(hipMemcpy(out_ann[f], frames[f].dst_ann, bytes, hipMemcpyDeviceToHost), "download");
-    if (frames[f].dst_miss) fail(hipMemcpy(out_miss[f], frames[f].dst_miss, bytes, hipMemcpyDeviceToHost), "download");
+    if (frames[f].dst_ann) job.download(out_ann[f], frames[f].dst_ann, bytes);
+    if (frames[f].dst_miss) job.download(out_miss[f], frames[f].dst_miss, bytes);
   }
-  for (void* p : d)
-    if (p) (void)hipFree(p);
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  if (!res) {
-    std::lock_guard<std::mutex> lock(g_view_mutex);
-    g_view_ms[device] = (double)ms;
-    g_view_ran[device] = true;
-  }
-  return res;
+  if (job.ok()) g_view_last.done(device, job.ms());
+  return job.status();
 }
 
 extern "C" int op_annotation_views_last_ms(int32_t device, double* ms) {
-  if (!ms) {
-    set_error("op_annotation_views_last_ms: null ms");
-    return OP_ERR_INVALID;
-  }
-  if (device < 0 || device >= kViewMaxDevices) {
-    set_error("op_annotation_views_last_ms: bad device " + std::to_string(device));
-    return OP_ERR_INVALID;
-  }
-  std::lock_guard<std::mutex> lock(g_view_mutex);
-  if (!g_view_ran[device]) {
-    set_error("op_annotation_views_last_ms: no op_annotation_views has completed on device " + std::to_string(device));
-    return OP_ERR_STATE;
-  }
-  *ms = g_view_ms[device];
-  return OP_OK;
+  return g_view_last.get("op_annotation_views_last_ms", "op_annotation_views", device, ms);
 }

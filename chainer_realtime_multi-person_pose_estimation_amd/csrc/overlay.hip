@@ -24,19 +24,18 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "common.hpp"
 #include "ctx.hpp"
 #include "cvlinear.hpp"
+#include "oneshot.hpp"
 
 namespace op {
 namespace {
 
 constexpr int kOvMaxSide = 16384;
-constexpr int kOvMaxDevices = 64;
 constexpr int kOvThreads = 256;
 constexpr int kOvTileW = 64, kOvTileH = 16, kOvPx = 4;  // kOvTileW / kOvPx threads per row, kOvTileH rows
 constexpr int kOvLdsFloats = 3584;                      // 14 KiB of staged map windows per workgroup
@@ -336,11 +335,6 @@ __global__ __launch_bounds__(kOvThreads) void overlay_tiles(OvArgs a) {
 }
 
 // ---- host ----
-int ov_invalid(const char* who, const std::string& msg) {
-  set_error(std::string(who) + ": " + msg);
-  return OP_ERR_INVALID;
-}
-
 // Lays the tiles of n frames (sizes set) out over the grid; makes no HIP call.
 int ov_tiles(const char* who, std::vector<OvFrame>& frames, int64_t* tiles) {
   *tiles = 0;
@@ -350,22 +344,32 @@ int ov_tiles(const char* who, std::vector<OvFrame>& frames, int64_t* tiles) {
     fr.tile0 = (int32_t)*tiles;
     *tiles += (int64_t)fr.tiles_x * ((fr.h + kOvTileH - 1) / kOvTileH);
   }
-  if (*tiles > INT32_MAX) return ov_invalid(who, "hw: more than 2^31 - 1 pixel tiles in the batch");
+  if (*tiles > INT32_MAX) return invalid(who, "hw: more than 2^31 - 1 pixel tiles in the batch");
   return OP_OK;
 }
 
-std::mutex g_ov_mutex;
-double g_ov_ms[kOvMaxDevices];
-bool g_ov_ran[kOvMaxDevices];
+LastMs g_ov_last;
 
-void ov_done(int device, float ms) {
-  if (device < 0 || device >= kOvMaxDevices) return;
-  std::lock_guard<std::mutex> lock(g_ov_mutex);
-  g_ov_ms[device] = (double)ms;
-  g_ov_ran[device] = true;
+// The frame table and (with a heat layer) the colour table in the job's buffers
+OvArgs ov_alloc(Job& job, int32_t n, bool any_heat) {
+  OvArgs a;
+  a.frames = (const OvFrame*)job.alloc((size_t)n * sizeof(OvFrame));
+  a.lut = (const uint8_t*)job.alloc(any_heat ? 768 : 0);
+  a.n = n;
+  return a;
 }
 
-int64_t ov_pad16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+// Uploads the frames (src, dst and the layers set) and the colour table, queues overlay_tiles; ends
+// the job's timing
+void ov_run(Job& job, const std::vector<OvFrame>& frames, const uint8_t* lut, int64_t tiles, const OvArgs& a) {
+  job.upload((void*)a.frames, frames.data(), frames.size() * sizeof(OvFrame));
+  if (a.lut) job.upload((void*)a.lut, lut, 768);
+  if (job.ok()) {
+    hipLaunchKernelGGL(overlay_tiles, dim3((unsigned)tiles), dim3(kOvThreads), 0, job.stream(), a);
+    job.check(hipGetLastError(), "overlay_tiles");
+  }
+  job.end();
+}
 
 }  // namespace
 }  // namespace op
@@ -377,14 +381,11 @@ extern "C" int op_overlay(int32_t device, int32_t n, const uint8_t* const* bgr, 
                           const float* const* heat, const int32_t* heat_chw, const uint8_t* const* mask,
                           const int32_t* mask_hw, const uint8_t* lut, uint8_t* const* out) {
   const char* who = "op_overlay";
-  if (n < 1 || n > (1 << 20)) return ov_invalid(who, "n must be in 1 .. 1048576");
-  if (!bgr) return ov_invalid(who, "null bgr");
-  if (!row_stride) return ov_invalid(who, "null row_stride");
-  if (!hw) return ov_invalid(who, "null hw");
-  if (!out) return ov_invalid(who, "null out");
-  if (pafs && !paf_chw) return ov_invalid(who, "null paf_chw");
-  if (heat && !heat_chw) return ov_invalid(who, "null heat_chw");
-  if (mask && !mask_hw) return ov_invalid(who, "null mask_hw");
+  if (n < 1 || n > (1 << 20)) return invalid(who, "n must be in 1 .. 1048576");
+  RC(check_frames(who, n, bgr, row_stride, hw, out));
+  if (pafs && !paf_chw) return invalid(who, "null paf_chw");
+  if (heat && !heat_chw) return invalid(who, "null heat_chw");
+  if (mask && !mask_hw) return invalid(who, "null mask_hw");
   auto side = [](int v) { return v >= 1 && v <= kOvMaxSide; };
   std::vector<OvFrame> frames((size_t)n);
   bool any_heat = false;
@@ -392,25 +393,20 @@ extern "C" int op_overlay(int32_t device, int32_t n, const uint8_t* const* bgr, 
     const std::string at = "frame " + std::to_string(f);
     OvFrame& fr = frames[f];
     memset(&fr, 0, sizeof(fr));
-    if (!side(hw[2 * f]) || !side(hw[2 * f + 1])) return ov_invalid(who, "hw: " + at + ": h, w must be in 1 .. 16384");
-    if (!bgr[f]) return ov_invalid(who, "bgr: " + at + ": null image");
-    if (!out[f]) return ov_invalid(who, "out: " + at + ": null image");
-    if (row_stride[f] < (int64_t)hw[2 * f + 1] * 3)
-      return ov_invalid(who, "row_stride: " + at + ": fewer than 3 w bytes per row");
     fr.h = hw[2 * f];
     fr.w = hw[2 * f + 1];
     if (pafs && pafs[f]) {
       const int32_t* d = paf_chw + 3 * f;
-      if (d[0] < 2 || d[0] % 2) return ov_invalid(who, "paf_chw: " + at + ": a positive, even channel count expected");
-      if (!side(d[1]) || !side(d[2])) return ov_invalid(who, "paf_chw: " + at + ": mh, mw must be in 1 .. 16384");
+      if (d[0] < 2 || d[0] % 2) return invalid(who, "paf_chw: " + at + ": a positive, even channel count expected");
+      if (!side(d[1]) || !side(d[2])) return invalid(who, "paf_chw: " + at + ": mh, mw must be in 1 .. 16384");
       fr.paf.c = d[0];
       fr.paf.mh = d[1];
       fr.paf.mw = d[2];
     }
     if (heat && heat[f]) {
       const int32_t* d = heat_chw + 3 * f;
-      if (d[0] < 1) return ov_invalid(who, "heat_chw: " + at + ": a channel count of at least 1 expected");
-      if (!side(d[1]) || !side(d[2])) return ov_invalid(who, "heat_chw: " + at + ": mh, mw must be in 1 .. 16384");
+      if (d[0] < 1) return invalid(who, "heat_chw: " + at + ": a channel count of at least 1 expected");
+      if (!side(d[1]) || !side(d[2])) return invalid(who, "heat_chw: " + at + ": mh, mw must be in 1 .. 16384");
       fr.heat.c = d[0];
       fr.heat.mh = d[1];
       fr.heat.mw = d[2];
@@ -418,107 +414,71 @@ extern "C" int op_overlay(int32_t device, int32_t n, const uint8_t* const* bgr, 
     }
     if (mask && mask[f]) {
       if (!side(mask_hw[2 * f]) || !side(mask_hw[2 * f + 1]))
-        return ov_invalid(who, "mask_hw: " + at + ": h, w must be in 1 .. 16384");
+        return invalid(who, "mask_hw: " + at + ": h, w must be in 1 .. 16384");
       fr.mkh = mask_hw[2 * f];
       fr.mkw = mask_hw[2 * f + 1];
     }
   }
-  if (any_heat && !lut) return ov_invalid(who, "null lut (a heat layer needs the 256 x 3 colour table)");
+  if (any_heat && !lut) return invalid(who, "null lut (a heat layer needs the 256 x 3 colour table)");
   int64_t tiles = 0;
-  int rc = ov_tiles(who, frames, &tiles);
-  if (rc) return rc;
-  int ndev = 0;
-  OP_HIP_CHECK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev || device >= kOvMaxDevices) return ov_invalid(who, "no HIP device " + std::to_string(device));
-  OP_HIP_CHECK(hipSetDevice(device));
+  RC(ov_tiles(who, frames, &tiles));
+  RC(use_device(who, device));
   // one buffer each for the frames in, the frames out (one layout: rows of 3 w bytes), the maps and the masks
   std::vector<int64_t> off(n + 1, 0), moff(2 * (size_t)n + 1, 0), koff(n + 1, 0);
   for (int f = 0; f < n; ++f) {
     const OvFrame& fr = frames[f];
-    off[f + 1] = off[f] + ov_pad16((int64_t)fr.h * fr.w * 3);
-    moff[2 * f + 1] = moff[2 * f] + ov_pad16((int64_t)fr.paf.c * fr.paf.mh * fr.paf.mw * 4);
-    moff[2 * f + 2] = moff[2 * f + 1] + ov_pad16((int64_t)fr.heat.c * fr.heat.mh * fr.heat.mw * 4);
-    koff[f + 1] = koff[f] + ov_pad16((int64_t)fr.mkh * fr.mkw);
+    off[f + 1] = off[f] + pad16((int64_t)fr.h * fr.w * 3);
+    moff[2 * f + 1] = moff[2 * f] + pad16((int64_t)fr.paf.c * fr.paf.mh * fr.paf.mw * 4);
+    moff[2 * f + 2] = moff[2 * f + 1] + pad16((int64_t)fr.heat.c * fr.heat.mh * fr.heat.mw * 4);
+    koff[f + 1] = koff[f] + pad16((int64_t)fr.mkh * fr.mkw);
   }
-  enum { FRAMES, SRC, DST, MAPS, MASKS, LUT, NBUF };
-  const size_t sizes[NBUF] = {frames.size() * sizeof(OvFrame), (size_t)off[n],  (size_t)off[n],
-                              (size_t)moff[2 * (size_t)n],     (size_t)koff[n], any_heat ? (size_t)768 : (size_t)0};
-  void* d[NBUF] = {};
-  hipEvent_t ev[2] = {};
-  int res = OP_OK;
-  auto fail = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess || res) return;
-    set_error(std::string("op_overlay: ") + what + ": " + hipGetErrorString(e));
-    res = OP_ERR_HIP;
-  };
-  for (int i = 0; i < NBUF && !res; ++i)
-    if (sizes[i]) fail(hipMalloc(&d[i], sizes[i]), "hipMalloc");
-  for (int i = 0; i < 2 && !res; ++i) fail(hipEventCreate(&ev[i]), "hipEventCreate");
-  if (!res) fail(hipEventRecord(ev[0], nullptr), "hipEventRecord");
-  for (int f = 0; f < n && !res; ++f) {
+  Job job(who, nullptr);
+  const OvArgs a = ov_alloc(job, n, any_heat);
+  uint8_t* src = (uint8_t*)job.alloc((size_t)off[n]);
+  uint8_t* dst = (uint8_t*)job.alloc((size_t)off[n]);
+  const char* maps = (const char*)job.alloc((size_t)moff[2 * (size_t)n]);
+  const uint8_t* masks = (const uint8_t*)job.alloc((size_t)koff[n]);
+  job.begin();
+  for (int f = 0; f < n && job.ok(); ++f) {
     OvFrame& fr = frames[f];
-    fr.src = (const uint8_t*)d[SRC] + off[f];
-    fr.dst = (uint8_t*)d[DST] + off[f];
+    fr.src = src + off[f];
+    fr.dst = dst + off[f];
     fr.src_stride = (int64_t)fr.w * 3;
-    fail(hipMemcpy2D((void*)fr.src, (size_t)fr.w * 3, bgr[f], (size_t)row_stride[f], (size_t)fr.w * 3, (size_t)fr.h,
-                     hipMemcpyHostToDevice),
-         "frame upload");
+    job.upload2d((void*)fr.src, (size_t)fr.w * 3, bgr[f], (size_t)row_stride[f], (size_t)fr.w * 3, (size_t)fr.h,
+                 "frame upload");
     OvLayer* layers[2] = {&fr.paf, &fr.heat};
     const float* host[2] = {fr.paf.c ? pafs[f] : nullptr, fr.heat.c ? heat[f] : nullptr};
-    for (int k = 0; k < 2 && !res; ++k) {
+    for (int k = 0; k < 2; ++k) {
       OvLayer& m = *layers[k];
       if (!m.c) continue;
-      m.p = (const float*)((const char*)d[MAPS] + moff[2 * f + k]);
+      m.p = (const float*)(maps + moff[2 * f + k]);
       m.cstr = (int64_t)m.mh * m.mw;
       m.rstr = m.mw;
       m.pstr = 1;
-      fail(hipMemcpy((void*)m.p, host[k], (size_t)m.c * m.mh * m.mw * 4, hipMemcpyHostToDevice), "map upload");
+      job.upload((void*)m.p, host[k], (size_t)m.c * m.mh * m.mw * 4, "map upload");
     }
-    if (fr.mkh && !res) {
-      fr.mask = (const uint8_t*)d[MASKS] + koff[f];
-      fail(hipMemcpy((void*)fr.mask, mask[f], (size_t)fr.mkh * fr.mkw, hipMemcpyHostToDevice), "mask upload");
+    if (fr.mkh) {
+      fr.mask = masks + koff[f];
+      job.upload((void*)fr.mask, mask[f], (size_t)fr.mkh * fr.mkw, "mask upload");
     }
   }
-  if (!res && any_heat) fail(hipMemcpy(d[LUT], lut, 768, hipMemcpyHostToDevice), "upload");
-  if (!res) fail(hipMemcpy(d[FRAMES], frames.data(), sizes[FRAMES], hipMemcpyHostToDevice), "upload");
-  if (!res) {
-    OvArgs a;
-    a.frames = (const OvFrame*)d[FRAMES];
-    a.lut = (const uint8_t*)d[LUT];
-    a.n = n;
-    hipLaunchKernelGGL(overlay_tiles, dim3((unsigned)tiles), dim3(kOvThreads), 0, nullptr, a);
-    fail(hipGetLastError(), "overlay_tiles");
-  }
-  if (!res) fail(hipEventRecord(ev[1], nullptr), "hipEventRecord");
-  if (!res) fail(hipDeviceSynchronize(), "kernel");
-  float ms = 0.0f;
-  if (!res) fail(hipEventElapsedTime(&ms, ev[0], ev[1]), "hipEventElapsedTime");
-  for (int f = 0; f < n && !res; ++f)
-    fail(hipMemcpy(out[f], frames[f].dst, (size_t)frames[f].h * frames[f].w * 3, hipMemcpyDeviceToHost), "download");
-  for (void* p : d)
-    if (p) (void)hipFree(p);
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  if (!res) ov_done(device, ms);
-  return res;
+  ov_run(job, frames, lut, tiles, a);
+  job.finish("kernel");
+  for (int f = 0; f < n; ++f) job.download(out[f], frames[f].dst, (size_t)frames[f].h * frames[f].w * 3);
+  if (job.ok()) g_ov_last.done(device, job.ms());
+  return job.status();
 }
 
 extern "C" int op_overlay_staged(op_ctx* c, int32_t first, int32_t n, int32_t layers, const uint8_t* lut,
                                  uint8_t* out) {
   const char* who = "op_overlay_staged";
-  if (!c) return ov_invalid(who, "null context");
-  if (n < 1 || n > (1 << 20)) return ov_invalid(who, "n must be in 1 .. 1048576");
-  if (!out) return ov_invalid(who, "null out");
-  if (layers & ~(OP_OVERLAY_PAFS | OP_OVERLAY_HEAT)) return ov_invalid(who, "layers: unknown bits");
-  if ((layers & OP_OVERLAY_HEAT) && !lut) return ov_invalid(who, "null lut (the heat layer needs the 256 x 3 colour table)");
-  if (c->st_n < 1) {
-    set_error("op_overlay_staged: no staged frames");
-    return OP_ERR_STATE;
-  }
-  if (first < 0 || first > c->st_n - n)
-    return ov_invalid(who, "first, n: frames " + std::to_string(first) + " .. " + std::to_string((int64_t)first + n - 1) +
-                               " are outside the " + std::to_string(c->st_n) + " staged frames");
-  if (c->st_h > kOvMaxSide || c->st_w > kOvMaxSide) return ov_invalid(who, "staged frames above 16384 in h or w");
+  if (!c) return invalid(who, "null context");
+  if (n < 1 || n > (1 << 20)) return invalid(who, "n must be in 1 .. 1048576");
+  if (!out) return invalid(who, "null out");
+  if (layers & ~(OP_OVERLAY_PAFS | OP_OVERLAY_HEAT)) return invalid(who, "layers: unknown bits");
+  if ((layers & OP_OVERLAY_HEAT) && !lut) return invalid(who, "null lut (the heat layer needs the 256 x 3 colour table)");
+  RC(staged_range(c, who, first, n));
+  if (c->st_h > kOvMaxSide || c->st_w > kOvMaxSide) return invalid(who, "staged frames above 16384 in h or w");
   RC(check_ctx(c, false));
   // the maps op_fetch_maps returns for these frames, where they lie
   int in_w, in_h, map_w, map_h;
@@ -566,57 +526,18 @@ extern "C" int op_overlay_staged(op_ctx* c, int32_t first, int32_t n, int32_t la
     if (layers & OP_OVERLAY_HEAT) fr.heat = heat;
   }
   int64_t tiles = 0;
-  int rc = ov_tiles(who, frames, &tiles);
-  if (rc) return rc;
-  const bool any_heat = (layers & OP_OVERLAY_HEAT) != 0;
-  enum { FRAMES, DST, LUT, NBUF };
-  const size_t sizes[NBUF] = {frames.size() * sizeof(OvFrame), fbytes * n, any_heat ? (size_t)768 : (size_t)0};
-  void* d[NBUF] = {};
-  hipEvent_t ev[2] = {};
-  int res = OP_OK;
-  auto fail = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess || res) return;
-    set_error(std::string("op_overlay_staged: ") + what + ": " + hipGetErrorString(e));
-    res = OP_ERR_HIP;
-  };
-  for (int i = 0; i < NBUF && !res; ++i)
-    if (sizes[i]) fail(hipMalloc(&d[i], sizes[i]), "hipMalloc");
-  for (int i = 0; i < 2 && !res; ++i) fail(hipEventCreate(&ev[i]), "hipEventCreate");
-  for (int f = 0; f < n && !res; ++f) frames[f].dst = (uint8_t*)d[DST] + (size_t)f * fbytes;
-  // everything below is ordered on the context stream, behind a queued run
-  if (!res) fail(hipEventRecord(ev[0], c->stream), "hipEventRecord");
-  if (!res) fail(hipMemcpyAsync(d[FRAMES], frames.data(), sizes[FRAMES], hipMemcpyHostToDevice, c->stream), "upload");
-  if (!res && any_heat) fail(hipMemcpyAsync(d[LUT], lut, 768, hipMemcpyHostToDevice, c->stream), "upload");
-  if (!res) {
-    OvArgs a;
-    a.frames = (const OvFrame*)d[FRAMES];
-    a.lut = (const uint8_t*)d[LUT];
-    a.n = n;
-    hipLaunchKernelGGL(overlay_tiles, dim3((unsigned)tiles), dim3(kOvThreads), 0, c->stream, a);
-    fail(hipGetLastError(), "overlay_tiles");
-  }
-  if (!res) fail(hipEventRecord(ev[1], c->stream), "hipEventRecord");
-  if (!res) fail(hipMemcpyAsync(out, d[DST], sizes[DST], hipMemcpyDeviceToHost, c->stream), "download");
-  // also after a failure: the vectors and the buffers must outlive what was queued
-  fail(hipStreamSynchronize(c->stream), "kernel");
-  float ms = 0.0f;
-  if (!res) fail(hipEventElapsedTime(&ms, ev[0], ev[1]), "hipEventElapsedTime");
-  for (void* p : d)
-    if (p) (void)hipFree(p);
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  if (!res) ov_done(c->device, ms);
-  return res;
+  RC(ov_tiles(who, frames, &tiles));
+  Job job(who, c->stream);  // everything is ordered on the context stream, behind a queued run
+  const OvArgs a = ov_alloc(job, n, (layers & OP_OVERLAY_HEAT) != 0);
+  uint8_t* dst = (uint8_t*)job.alloc(fbytes * n);
+  for (int f = 0; f < n && job.ok(); ++f) frames[f].dst = dst + (size_t)f * fbytes;
+  job.begin();
+  ov_run(job, frames, lut, tiles, a);
+  job.download(out, dst, fbytes * n);
+  if (job.finish("kernel") == OP_OK) g_ov_last.done(c->device, job.ms());
+  return job.status();
 }
 
 extern "C" int op_overlay_last_ms(int32_t device, double* ms) {
-  if (!ms) return ov_invalid("op_overlay_last_ms", "null ms");
-  if (device < 0 || device >= kOvMaxDevices) return ov_invalid("op_overlay_last_ms", "bad device " + std::to_string(device));
-  std::lock_guard<std::mutex> lock(g_ov_mutex);
-  if (!g_ov_ran[device]) {
-    set_error("op_overlay_last_ms: no op_overlay or op_overlay_staged has completed on device " + std::to_string(device));
-    return OP_ERR_STATE;
-  }
-  *ms = g_ov_ms[device];
-  return OP_OK;
+  return g_ov_last.get("op_overlay_last_ms", "op_overlay or op_overlay_staged", device, ms);
 }

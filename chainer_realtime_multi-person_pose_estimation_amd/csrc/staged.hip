@@ -67,6 +67,17 @@ void staged_sizes(op_ctx* c, int* in_w, int* in_h, int* map_w, int* map_h) {
   optimal_size(c->st_h, c->st_w, c->prm.heatmap_size, 8, map_w, map_h);
 }
 
+int staged_range(op_ctx* c, const char* who, int32_t first, int32_t n) {
+  if (c->st_n < 1) {
+    set_error(std::string(who) + ": no staged frames");
+    return OP_ERR_STATE;
+  }
+  if (first < 0 || first > c->st_n - n)
+    return invalid(who, "first, n: frames " + std::to_string(first) + " .. " + std::to_string((int64_t)first + n - 1) +
+                            " are outside the " + std::to_string(c->st_n) + " staged frames");
+  return OP_OK;
+}
+
 // One frame (h x w x 3 u8, row stride row_stride) from caller memory into d_frames on the compute
 // stream, through the context's page-locked staging buffer (op_detect / op_detect_precise).
 int upload_one_frame(op_ctx* c, const uint8_t* bgr, int h, int w, int64_t row_stride) {

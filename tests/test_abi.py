@@ -177,6 +177,30 @@ def test_every_unit_is_linked():
         assert os.path.isfile(os.path.join(csrc, s + ".cpp")), "OBJS names %s.o, which has no source" % s
 
 
+@pytest.mark.parametrize("name, ran", [
+    ("op_augment_last_ms", ["op_augment"]),
+    ("op_ignore_masks_last_ms", ["op_ignore_masks"]),
+    ("op_annotation_views_last_ms", ["op_annotation_views"]),
+    ("op_draw_last_ms", ["op_draw", "op_draw_staged"]),
+    ("op_overlay_last_ms", ["op_overlay", "op_overlay_staged"]),
+    ("op_body_last_ms", ["op_body_rois", "op_body_rois_staged"]),
+])
+def test_last_ms_refusals(lib, name, ran):
+    """The six op_*_last_ms entry points (host only, one record type behind them): a null ms and a
+    device outside 0 .. 63 are OP_ERR_INVALID; a device no call has completed on (63: nothing in the
+    suite runs there) is OP_ERR_STATE, and the message names the entry point and the calls it times."""
+    fn = getattr(lib.lib(), name)
+    ms = ctypes.c_double(-1.0)
+    assert fn(0, None) == lib.OP_ERR_INVALID
+    assert lib.last_error() == name + ": null ms"
+    for device in (-1, 64):
+        assert fn(device, ctypes.byref(ms)) == lib.OP_ERR_INVALID
+        assert lib.last_error() == "%s: bad device %d" % (name, device)
+    assert fn(63, ctypes.byref(ms)) == lib.OP_ERR_STATE
+    assert lib.last_error() == "%s: no %s has completed on device 63" % (name, " or ".join(ran))
+    assert ms.value == -1.0
+
+
 @pytest.mark.parametrize("preset", [None, "4", "16"])
 def test_loader_leaves_the_environment_alone(preset):
     """Loading the library does not rewrite the host process's environment (round 3: the
