@@ -46,6 +46,7 @@ EXPORTED = (
     "op_overlay", "op_overlay_staged", "op_overlay_last_ms",
     "op_cpm_detect_rois_staged", "op_cpm_set_roi_batch",
     "op_body_rois", "op_body_rois_staged", "op_body_last_ms",
+    "op_keypoint_match", "op_keypoint_match_staged", "op_keypoint_last_ms",
 )
 ARCH = {"facenet": 1, "handnet": 2}
 CPM_PROBE_HI = 256  # OP_CPM_PROBE_HI
@@ -212,6 +213,9 @@ def lib():
         "op_body_rois": ([I32, I32, P, P, P, P], ctypes.c_int),
         "op_body_rois_staged": ([P, I32, I32, I32, P, P, P, P, P], ctypes.c_int),
         "op_body_last_ms": ([I32, P], ctypes.c_int),
+        "op_keypoint_match": ([I32, I32] + [P] * 9 + [I32, I32, P, I32, P, P] + [P] * 6, ctypes.c_int),
+        "op_keypoint_match_staged": ([P, I32, I32] + [P] * 7 + [I32, I32, P, I32, P, P] + [P] * 9, ctypes.c_int),
+        "op_keypoint_last_ms": ([I32, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -730,6 +734,29 @@ class Context(object):
             check(rc, "op_body_rois_staged")
         return count, status, unit, box, state
 
+    def keypoint_match(self, first, n, gts, joint_map=None, max_dets=None, thrs=None, area_rng=None, sigmas=None,
+                       want_oks=False):
+        """COCO keypoint matching of the persons of staged frames [first, first + n) against ``gts``
+        (per frame ``keypoint_eval.gt_tables``' tuple), on the device from the result rows where they
+        lie (op_keypoint_match_staged; keypoint_eval.match_np states it) -> (frame_status (n,), the
+        list of per-frame records).  A frame whose status is not OP_OK comes back with no detections:
+        the caller takes it through ``fetch_result`` and ``_lib.keypoint_match``."""
+        from . import keypoint_eval as K
+        n = int(n)
+        if len(gts) != n:
+            raise ValueError("Context.keypoint_match: %d frames, %d ground-truth tables" % (n, len(gts)))
+        g = _KeypointCall(gts, max_dets, thrs, area_rng, sigmas, want_oks)
+        jm = np.ascontiguousarray(K.joint_map() if joint_map is None else joint_map, np.int32)
+        if jm.shape != (17,):
+            raise ValueError("Context.keypoint_match: joint_map has 17 entries")
+        status = np.zeros(max(n, 1), np.int32)
+        count = np.zeros(max(n, 1), np.int32)
+        scores = np.zeros((max(n, 1), g.M), np.float64)
+        g.outputs(n)
+        check(lib().op_keypoint_match_staged(self.h, int(first), n, ptr(jm), *(g.gt_args() + g.const_args() + [
+            ptr(status), ptr(count), ptr(scores)] + g.out_args())), "op_keypoint_match_staged")
+        return status[:n], g.records(n, [scores[i, :min(int(count[i]), g.M)].copy() for i in range(n)])
+
     def fetch_maps(self, first=0, n=1):
         """Network maps of staged frames [first, first+n): (pafs (n,38,h,w), heatmaps (n,19,h,w)) --
         the last-stage maps of run_staged, or the averaged full-resolution maps of run_staged_precise."""
@@ -793,6 +820,113 @@ def body_last_ms(device=0):
     that completed on this device."""
     ms = ctypes.c_double()
     check(lib().op_body_last_ms(int(device), ctypes.byref(ms)), "op_body_last_ms")
+    return ms.value
+
+
+class _KeypointCall(object):
+    """The ground-truth tables, constants and output arrays of one op_keypoint_match* call, and the
+    per-frame records (keypoint_eval.match_np's dict) cut out of the outputs."""
+
+    def __init__(self, gts, max_dets, thrs, area_rng, sigmas, want_oks):
+        from . import keypoint_eval as K
+        self.M = int(K.MAX_DETS if max_dets is None else max_dets)
+        self.thrs = np.ascontiguousarray(K.OKS_THRS if thrs is None else thrs, np.float64).reshape(-1)
+        self.rng = np.ascontiguousarray(K.AREA_RNG if area_rng is None else area_rng, np.float64).reshape(-1, 2)
+        self.sig = np.ascontiguousarray(K.KPT_SIGMAS if sigmas is None else sigmas, np.float64).reshape(-1)
+        if self.sig.shape != (17,):
+            raise ValueError("keypoint_match: sigmas has 17 entries")
+        if not 1 <= self.M <= 64:
+            raise ValueError("keypoint_match: max_dets must be in 1 .. 64")
+        self.want_oks = bool(want_oks)
+        self.T, self.A = len(self.thrs), len(self.rng)
+        counts = [len(np.asarray(g[1]).reshape(-1)) for g in gts]
+        self.off = np.zeros(len(gts) + 1, np.int32)
+        self.off[1:] = np.cumsum(counts)
+        G = self.G = int(self.off[-1])
+
+        def cat(k, shape, dtype):
+            out = np.zeros((max(G, 1),) + shape, dtype)
+            if G:
+                out[:G] = np.concatenate([np.asarray(g[k], dtype).reshape((-1,) + shape) for g in gts])
+            return out
+
+        self.kpts, self.area, self.bbox = cat(0, (17, 3), np.float64), cat(1, (), np.float64), cat(2, (4,), np.float64)
+        self.ignore = cat(3, (), np.uint8) if not G else np.ascontiguousarray(
+            np.concatenate([np.asarray(g[3]).reshape(-1) != 0 for g in gts]), np.uint8)
+        self.crowd = cat(4, (), np.uint8) if not G else np.ascontiguousarray(
+            np.concatenate([np.asarray(g[4]).reshape(-1) != 0 for g in gts]), np.uint8)
+
+    def gt_args(self):
+        return [ptr(self.off), ptr(self.kpts), ptr(self.area), ptr(self.bbox), ptr(self.ignore), ptr(self.crowd)]
+
+    def const_args(self):
+        return [self.M, self.T, ptr(self.thrs), self.A, ptr(self.rng), ptr(self.sig)]
+
+    def outputs(self, n):
+        M, A, T, G = self.M, self.A, self.T, self.G
+        self.dt_order = np.full((max(n, 1), M), -1, np.int32)
+        self.oks = np.zeros(max(M * G, 1), np.float64) if self.want_oks else None
+        self.dt_match = np.full((max(n, 1), A, T, M), -1, np.int32)
+        self.dt_ignore = np.zeros((max(n, 1), A, T, M), np.uint8)
+        self.gt_match = np.full(max(A * T * G, 1), -1, np.int32)
+        self.gt_ig = np.zeros(max(A * G, 1), np.uint8)
+
+    def out_args(self):
+        return [ptr(self.dt_order), ptr(self.oks), ptr(self.dt_match), ptr(self.dt_ignore), ptr(self.gt_match),
+                ptr(self.gt_ig)]
+
+    def records(self, n, scores):
+        """scores: per frame the kept detections' scores, in order."""
+        M, A, T = self.M, self.A, self.T
+        out = []
+        for f in range(n):
+            g0, g1 = int(self.off[f]), int(self.off[f + 1])
+            G = g1 - g0
+            D = int(np.count_nonzero(self.dt_order[f] >= 0))
+            rec = {"dt_order": self.dt_order[f, :D].copy(), "dt_scores": np.asarray(scores[f], np.float64)[:D].copy(),
+                   "dt_match": self.dt_match[f, :, :, :D].copy(), "dt_ignore": self.dt_ignore[f, :, :, :D].copy(),
+                   "gt_match": self.gt_match[A * T * g0:A * T * g1].reshape(A, T, G).copy(),
+                   "gt_ignore": self.gt_ig[A * g0:A * g1].reshape(A, G).copy()}
+            if self.want_oks:
+                rec["oks"] = self.oks[M * g0:M * g0 + D * G].reshape(D, G).copy()
+            out.append(rec)
+        return out
+
+
+def keypoint_match(dets, gts, device=0, max_dets=None, thrs=None, area_rng=None, sigmas=None, want_oks=True):
+    """COCO keypoint matching of a batch of images on the device (op_keypoint_match), bit-identical
+    to keypoint_eval.match_np per image: ``dets`` per image (kpts (D, 17, 3), scores (D,)), ``gts``
+    per image ``keypoint_eval.gt_tables``' tuple -> the list of per-image records (match_np's dict;
+    ``oks`` only when asked for).  The constants default to keypoint_eval's."""
+    n = len(dets)
+    if len(gts) != n:
+        raise ValueError("keypoint_match: %d images of detections, %d of ground truths" % (n, len(gts)))
+    g = _KeypointCall(gts, max_dets, thrs, area_rng, sigmas, want_oks)
+    kp = [np.asarray(k, np.float64).reshape(-1, 17, 3) for k, _ in dets]
+    sc = [np.asarray(s, np.float64).reshape(-1) for _, s in dets]
+    for i in range(n):
+        if len(kp[i]) != len(sc[i]):
+            raise ValueError("keypoint_match: image %d: %d detections, %d scores" % (i, len(kp[i]), len(sc[i])))
+    off = np.zeros(n + 1, np.int32)
+    off[1:] = np.cumsum([len(s) for s in sc])
+    D = int(off[-1])
+    kpts = np.zeros((max(D, 1), 17, 3), np.float64)
+    scores = np.zeros(max(D, 1), np.float64)
+    if D:
+        kpts[:D] = np.concatenate(kp)
+        scores[:D] = np.concatenate(sc)
+    g.outputs(n)
+    if n:
+        check(lib().op_keypoint_match(int(device), n, ptr(off), ptr(kpts), ptr(scores), *(
+            g.gt_args() + g.const_args() + g.out_args())), "op_keypoint_match")
+    return g.records(n, [sc[f][g.dt_order[f][g.dt_order[f] >= 0]] for f in range(n)])
+
+
+def keypoint_last_ms(device=0):
+    """Device time (uploads + kernel, stream events) of the last ``keypoint_match`` /
+    ``Context.keypoint_match`` that completed on this device."""
+    ms = ctypes.c_double()
+    check(lib().op_keypoint_last_ms(int(device), ctypes.byref(ms)), "op_keypoint_last_ms")
     return ms.value
 
 

@@ -1,6 +1,6 @@
-// What the one-shot device calls share (labels, augment, masks, maskview, draw, overlay, body: build
-// tables on the host, allocate, upload, run one to three kernels, time them, download, free): the
-// device selection, the scoped job that owns the buffers, the events and the first error, and the
+// What the one-shot device calls share (labels, augment, masks, maskview, draw, overlay, body,
+// keypoint: build tables on the host, allocate, upload, run one to three kernels, time them,
+// download, free): the device selection, the scoped job that owns the buffers, the events and the first error, and the
 // per-device "last device time" record.  Each unit keeps its own sequence of steps and its own
 // kernel launches.  Nothing here is part of the library's interface.
 #pragma once

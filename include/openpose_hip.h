@@ -833,6 +833,55 @@ int op_body_rois_staged(op_ctx* ctx, int32_t first, int32_t n, int32_t cap, int3
  * op_body_rois_staged that completed on `device`; OP_ERR_STATE before the first. */
 int op_body_last_ms(int32_t device, double* ms);
 
+/* ---- COCO keypoint matching (keypoint_eval.py; COCOeval's computeOks and evaluateImg for iouType
+ * 'keypoints', restated there in NumPy: parity with pycocotools itself is unpinned) ----
+ * One kernel launch per call, one workgroup per frame (image), f64 with every operation rounded on
+ * its own: the detections ranked by descending score (stable; a NaN score as -inf) and cut to
+ * max_dets; the object keypoint similarity of every kept detection and ground truth; per area range
+ * and threshold the greedy match.  Bit-identical to keypoint_eval.match_np on every output.
+ * Frame f's detections are rows [dt_offsets[f], dt_offsets[f + 1]) of dt_kpts (17 x 3 f64 each: x, y,
+ * v in COCO's keypoint order) and dt_scores; its ground truths rows [gt_offsets[f], gt_offsets[f + 1])
+ * of gt_kpts (17 x 3), gt_area, gt_bbox (x, y, w, h), gt_ignore and gt_iscrowd (u8).  thrs: n_thrs
+ * OKS thresholds; area_rng: n_areas (lo, hi) pairs; sigmas: the 17 per-keypoint constants.
+ * Outputs, with M = max_dets, A = n_areas, T = n_thrs, D' = min(detections, M), g0 = gt_offsets[f] and
+ * G the frame's ground truths:
+ *   dt_order  [f][M]        the kept detections' indices within the frame, -1 past D'
+ *   oks       [M * g0 + r * G + g]  of kept detection r and ground truth g; NULL: not wanted
+ *   dt_match  [f][A][T][M]  the ground truth (index within the frame) detection r matched, -1 for none
+ *   dt_ignore [f][A][T][M]  u8
+ *   gt_match  [A * T * g0 + (a * T + t) * G + g]  the detection (index within the frame), -1 for none
+ *   gt_ignore_out [A * g0 + a * G + g]  u8: gt_ignore or the area outside range a
+ * n_frames == 0: OP_OK.  OP_ERR_INVALID, with nothing written: a null pointer, offsets that do not
+ * start at 0 or decrease, max_dets outside 1 .. 64, more than 128 ground truths in a frame (the
+ * message names it), n_thrs outside 1 .. 16, n_areas outside 1 .. 4, a gt area that is not finite or
+ * negative, a gt bbox, threshold, range or sigma that is not finite, a sigma that is not positive. */
+int op_keypoint_match(int32_t device, int32_t n_frames, const int32_t* dt_offsets, const double* dt_kpts,
+                      const double* dt_scores, const int32_t* gt_offsets, const double* gt_kpts,
+                      const double* gt_area, const double* gt_bbox, const uint8_t* gt_ignore,
+                      const uint8_t* gt_iscrowd, int32_t max_dets, int32_t n_thrs, const double* thrs,
+                      int32_t n_areas, const double* area_rng, const double* sigmas, int32_t* dt_order, double* oks,
+                      int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore_out);
+/* The same with the detections read from the result rows (poses and scores) of staged frames
+ * [first, first + n) where the post-process left them, after ctx's queued work; joint_map[i] = the
+ * pose joint (0 .. 17) that is COCO keypoint i, applied by the kernel.  Only the ground-truth tables
+ * are uploaded and only the match block comes back (one asynchronous copy, one synchronisation); the
+ * result rows are neither copied nor written.  Further outputs: frame_status[i] = the frame's status
+ * (a frame over the batched post-process caps has OP_ERR_CAPACITY and no detections here: the caller
+ * takes it through op_fetch_result and op_keypoint_match), dt_count[i] = persons found,
+ * dt_scores [i][M] = the kept detections' scores in order (0 past D').  OP_ERR_STATE when nothing is
+ * staged or no run has left results of the frames, OP_ERR_INVALID for a range outside the staged set
+ * and for everything op_keypoint_match refuses. */
+int op_keypoint_match_staged(op_ctx* ctx, int32_t first, int32_t n, const int32_t* joint_map,
+                             const int32_t* gt_offsets, const double* gt_kpts, const double* gt_area,
+                             const double* gt_bbox, const uint8_t* gt_ignore, const uint8_t* gt_iscrowd,
+                             int32_t max_dets, int32_t n_thrs, const double* thrs, int32_t n_areas,
+                             const double* area_rng, const double* sigmas, int32_t* frame_status, int32_t* dt_count,
+                             double* dt_scores, int32_t* dt_order, double* oks, int32_t* dt_match, uint8_t* dt_ignore,
+                             int32_t* gt_match, uint8_t* gt_ignore_out);
+/* Device time (ms, stream events) of the uploads and the kernel of the last op_keypoint_match or
+ * op_keypoint_match_staged that completed on `device`; OP_ERR_STATE before the first. */
+int op_keypoint_last_ms(int32_t device, double* ms);
+
 #ifdef __cplusplus
 }
 #endif
