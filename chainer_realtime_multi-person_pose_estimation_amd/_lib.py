@@ -47,6 +47,8 @@ EXPORTED = (
     "op_cpm_detect_rois_staged", "op_cpm_set_roi_batch",
     "op_body_rois", "op_body_rois_staged", "op_body_last_ms",
     "op_keypoint_match", "op_keypoint_match_staged", "op_keypoint_last_ms",
+    "op_jpeg_probe", "op_jpeg_coefficients", "op_jpeg_block_in_range", "op_jpeg_decode", "op_jpeg_stage",
+    "op_jpeg_set_threads", "op_jpeg_last_ms",
 )
 ARCH = {"facenet": 1, "handnet": 2}
 CPM_PROBE_HI = 256  # OP_CPM_PROBE_HI
@@ -89,6 +91,14 @@ class OpDrawPrim(ctypes.Structure):
 
 
 OP_DRAW_LINE, OP_DRAW_DISC, OP_DRAW_BLEND = range(3)
+
+
+class OpJpegInfo(ctypes.Structure):
+    """op_jpeg_info (include/openpose_hip.h): what a file's headers say (op_jpeg_probe)."""
+    _fields_ = [("status", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("components", ctypes.c_int32),
+                ("hs", ctypes.c_int32), ("vs", ctypes.c_int32), ("blocks_w", ctypes.c_int32 * 3),
+                ("blocks_h", ctypes.c_int32 * 3), ("n_blocks", ctypes.c_int64)]
+
 
 _lib = None
 
@@ -216,6 +226,13 @@ def lib():
         "op_keypoint_match": ([I32, I32] + [P] * 9 + [I32, I32, P, I32, P, P] + [P] * 6, ctypes.c_int),
         "op_keypoint_match_staged": ([P, I32, I32] + [P] * 7 + [I32, I32, P, I32, P, P] + [P] * 9, ctypes.c_int),
         "op_keypoint_last_ms": ([I32, P], ctypes.c_int),
+        "op_jpeg_probe": ([P, I64, P], ctypes.c_int),
+        "op_jpeg_coefficients": ([P, I64, P, I64, P, P], ctypes.c_int),
+        "op_jpeg_block_in_range": ([P, P, P], ctypes.c_int),
+        "op_jpeg_decode": ([I32, I32, P, P, P, P], ctypes.c_int),
+        "op_jpeg_stage": ([P, I32, P, P, P, I32, I32, P], ctypes.c_int),
+        "op_jpeg_set_threads": ([I32], ctypes.c_int),
+        "op_jpeg_last_ms": ([I32, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -645,6 +662,24 @@ class Context(object):
         n, h, w, c = frames.shape
         check(lib().op_stage_frames(self.h, ptr(frames), n, h, w), "op_stage_frames")
 
+    def stage_jpegs(self, datas, h, w, bgr=None):
+        """Stage files instead of pixels (op_jpeg_stage): frame f from ``bgr[f]`` ((h, w, 3) uint8) where
+        that is given, else decoded on the device from ``datas[f]`` (bytes) straight into the staged
+        set -> the per-frame OP_JPEG_* statuses (a frame with a non-zero status is staged as zeros)."""
+        n = len(datas)
+        bgr = list(bgr) if bgr is not None else [None] * n
+        if len(bgr) != n:
+            raise ValueError("Context.stage_jpegs: %d files, %d bgr entries" % (n, len(bgr)))
+        keep = [np.ascontiguousarray(b, dtype=np.uint8) if b is not None else None for b in bgr]
+        for b in keep:
+            if b is not None and b.shape != (h, w, 3):
+                raise ValueError("Context.stage_jpegs: a bgr frame of shape %r, not (%d, %d, 3)" % (b.shape, h, w))
+        files, data_p, size_p = _jpeg_files([d if k is None else None for d, k in zip(datas, keep)])
+        bgr_p = (ctypes.c_void_p * max(n, 1))(*[b.ctypes.data if b is not None else None for b in keep])
+        status = np.zeros(max(n, 1), np.int32)
+        check(lib().op_jpeg_stage(self.h, n, data_p, size_p, bgr_p, int(h), int(w), ptr(status)), "op_jpeg_stage")
+        return status[:n]
+
     def upload_frames(self, frames):
         """Asynchronous staging (op_upload_frames): the next run_staged* uses these frames; keep
         `frames` (ideally a PinnedFrames array) unchanged until the copy has completed
@@ -799,6 +834,68 @@ class Context(object):
                                         ctypes.byref(by)), "op_profile_read")
             out[name] = (ms.value, n.value, fl.value, by.value)
         return out
+
+
+def _jpeg_files(datas):
+    """-> (the buffers kept alive, a void* array of their addresses (null for None), an int64 array of sizes)."""
+    files = [np.frombuffer(d, np.uint8) if d is not None and len(d) else None for d in datas]
+    empty = np.zeros(1, np.uint8)  # an empty file still has an address
+    addr = [(f if f is not None else empty).ctypes.data if d is not None else None for f, d in zip(files, datas)]
+    data_p = (ctypes.c_void_p * max(len(datas), 1))(*addr)
+    size_p = (ctypes.c_int64 * max(len(datas), 1))(*[len(d) if d is not None else 0 for d in datas])
+    return (files, empty), data_p, size_p
+
+
+def jpeg_probe(data):
+    """op_jpeg_probe -> OpJpegInfo (headers only, on the host)."""
+    info = OpJpegInfo()
+    keep, data_p, size_p = _jpeg_files([data])
+    check(lib().op_jpeg_probe(data_p[0], size_p[0], ctypes.byref(info)), "op_jpeg_probe")
+    return info
+
+
+def jpeg_coefficients(data):
+    """op_jpeg_coefficients -> (status, info, coef (n_blocks, 64) int16, qt (3, 64) uint16): the host's
+    entropy decode of one file (jpeg.coefficients_np states it)."""
+    info = jpeg_probe(data)
+    coef = np.zeros((max(int(info.n_blocks), 1), 64), np.int16)
+    qt = np.zeros((3, 64), np.uint16)
+    status = ctypes.c_int32(-1)
+    keep, data_p, size_p = _jpeg_files([data])
+    check(lib().op_jpeg_coefficients(data_p[0], size_p[0], ptr(coef), coef.size, ptr(qt), ctypes.byref(status)),
+          "op_jpeg_coefficients")
+    return status.value, info, coef[:int(info.n_blocks)], qt
+
+
+def jpeg_block_in_range(coef, q):
+    coef = np.ascontiguousarray(coef, np.int16).reshape(64)
+    q = np.ascontiguousarray(q, np.uint16).reshape(64)
+    out = ctypes.c_int32(-1)
+    check(lib().op_jpeg_block_in_range(ptr(coef), ptr(q), ctypes.byref(out)), "op_jpeg_block_in_range")
+    return bool(out.value)
+
+
+def jpeg_decode(datas, outs, device=0):
+    """op_jpeg_decode: ``outs[f]`` a contiguous (h, w, 3) uint8 array (or None for a frame the probe
+    turned down) -> statuses (n,) int32."""
+    n = len(datas)
+    keep, data_p, size_p = _jpeg_files(datas)
+    out_p = (ctypes.c_void_p * max(n, 1))(*[o.ctypes.data if o is not None else None for o in outs])
+    status = np.zeros(max(n, 1), np.int32)
+    check(lib().op_jpeg_decode(int(device), n, data_p, size_p, out_p, ptr(status)), "op_jpeg_decode")
+    return status[:n]
+
+
+def jpeg_set_threads(threads):
+    """Threads of the entropy-decode pool (op_jpeg_set_threads): 1 .. 64, 0 for the default again."""
+    check(lib().op_jpeg_set_threads(int(threads)), "op_jpeg_set_threads")
+
+
+def jpeg_last_ms(device=0):
+    """(host entropy-decode ms, device ms) of the last op_jpeg_decode / op_jpeg_stage on ``device``."""
+    ms = (ctypes.c_double * 2)()
+    check(lib().op_jpeg_last_ms(int(device), ms), "op_jpeg_last_ms")
+    return ms[0], ms[1]
 
 
 def body_rois(poses, device=0):

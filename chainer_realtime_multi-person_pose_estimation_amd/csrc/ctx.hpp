@@ -206,6 +206,12 @@ struct op_ctx {
   // async copy on the compute stream -- no pageable or 2D copy path of the HIP runtime is involved
   uint8_t* up_pinned = nullptr;
   size_t up_pinned_bytes = 0;
+  // op_jpeg_stage: the page-locked staging of a batch ([frame table | coefficient blocks | frames
+  // given as pixels]) and its device side ([frame table | coefficient blocks | component planes])
+  uint8_t* jpeg_pinned = nullptr;
+  size_t jpeg_pinned_bytes = 0;
+  uint8_t* d_jpeg = nullptr;
+  size_t jpeg_bytes = 0;
   // uncapped post-process: the last batched post-process's input (to re-run one frame) and the
   // one-frame big-mode buffers sized from that frame's own counts
   op::PostRecord post_rec;
@@ -257,6 +263,11 @@ int stage_maps_dev(op_ctx* c, const float* maps, int n, int lh, int lw, float** 
 int take_upload(op_ctx* c);
 void staged_sizes(op_ctx* c, int* in_w, int* in_h, int* map_w, int* map_h);
 int upload_one_frame(op_ctx* c, const uint8_t* bgr, int h, int w, int64_t row_stride);
+// A new staged frame set, in two steps around whatever fills d_frames (op_stage_frames' copy,
+// op_jpeg_stage's kernels): a pending op_upload_frames is replaced and d_frames holds `bytes`; then,
+// the stream idle, the captured graph is dropped on a geometry change and the set is n frames of h x w
+int stage_reserve(op_ctx* c, size_t bytes);
+int stage_commit(op_ctx* c, int n, int h, int w);
 // "no staged frames" (OP_ERR_STATE), or frames first .. first + n - 1 (n >= 1) outside them
 int staged_range(op_ctx* c, const char* who, int32_t first, int32_t n);
 #pragma GCC visibility pop

@@ -295,6 +295,9 @@ int op_destroy(op_ctx* c) {
   if (c->d_psum) hipFree(c->d_psum);
   if (c->host_stage) hipHostFree(c->host_stage);
   if (c->up_pinned) hipHostFree(c->up_pinned);
+  if (c->jpeg_pinned) hipHostFree(c->jpeg_pinned);
+  guard_forget(c->d_jpeg, c->jpeg_bytes + g_guard);
+  if (c->d_jpeg) hipFree(c->d_jpeg);
   for (auto& k : c->keep) {
     if (k.h_rows) hipHostFree(k.h_rows);
     if (k.maps) hipFree(k.maps);

@@ -96,6 +96,24 @@ int upload_one_frame(op_ctx* c, const uint8_t* bgr, int h, int w, int64_t row_st
   return OP_OK;
 }
 
+int stage_reserve(op_ctx* c, size_t bytes) {
+  c->up_slot = -1;  // a pending op_upload_frames is replaced
+  return grow_buffer(c, (void**)&c->d_frames, &c->frames_bytes, bytes, "frames");
+}
+
+int stage_commit(op_ctx* c, int n, int h, int w) {
+  if (c->st_n != n || c->st_h != h || c->st_w != w) {
+    if (c->gexec) {
+      hipGraphExecDestroy(c->gexec);
+      c->gexec = nullptr;
+    }
+  }
+  c->st_n = n;
+  c->st_h = h;
+  c->st_w = w;
+  return OP_OK;
+}
+
 }  // namespace op
 
 extern "C" {
@@ -156,20 +174,10 @@ int op_stage_frames(op_ctx* c, const uint8_t* frames, int32_t n, int32_t h, int3
     return OP_ERR_INVALID;
   }
   const size_t bytes = (size_t)n * h * w * 3;
-  c->up_slot = -1;  // a pending op_upload_frames is replaced
-  RC(grow_buffer(c, (void**)&c->d_frames, &c->frames_bytes, bytes, "frames"));
+  RC(stage_reserve(c, bytes));
   OP_HIP_CHECK(hipMemcpyAsync(c->d_frames, frames, bytes, hipMemcpyHostToDevice, c->stream));
   OP_HIP_CHECK(hipStreamSynchronize(c->stream));
-  if (c->st_n != n || c->st_h != h || c->st_w != w) {
-    if (c->gexec) {
-      hipGraphExecDestroy(c->gexec);
-      c->gexec = nullptr;
-    }
-  }
-  c->st_n = n;
-  c->st_h = h;
-  c->st_w = w;
-  return OP_OK;
+  return stage_commit(c, n, h, w);
 }
 
 int op_stage_maps(op_ctx* c, const float* maps, int32_t n, int32_t mh, int32_t mw) {

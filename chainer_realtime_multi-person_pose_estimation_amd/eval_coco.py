@@ -8,7 +8,8 @@ print, as keypoint_eval.py states it (parity with pycocotools itself is unpinned
 
 Every image of the annotations file takes part, ids sorted, with or without persons and with or
 without detections.  The frames are read with ``draw.read_bgr`` (PIL) from ``--images`` /
-``images[*].file_name`` and bucketed by (h, w); each bucket is staged in chunks of at most
+``images[*].file_name`` (with ``--device-jpeg`` baseline JPEG files are decoded on the device instead,
+the same pixels: jpeg.py) and bucketed by (h, w); each bucket is staged in chunks of at most
 ``--batch`` frames through ``PoseDetector.run_staged``, and ``keypoint_eval.evaluate_staged``
 matches a chunk's poses against its ground truths on the device, where the post-process left them.
 The per-image records are accumulated once at the end, on the host.  ``--weights`` takes what
@@ -51,16 +52,22 @@ def run_detector(images, args):
     for i, (_, h, w, _, _) in enumerate(images):
         buckets.setdefault((h, w), []).append(i)
     records, entries = [None] * len(images), [None] * len(images)
+    routes = {"device": 0, "host": 0}
     for (h, w), members in sorted(buckets.items()):
         for start in range(0, len(members), args.batch):
             chunk = members[start:start + args.batch]
-            frames = np.empty((len(chunk), h, w, 3), np.uint8)
-            for k, i in enumerate(chunk):
-                img = read_bgr(os.path.join(args.images, images[i][4]))
-                if img.shape != (h, w, 3):
-                    raise ValueError("%s is %d x %d, the annotations say %d x %d" % (images[i][4], img.shape[0], img.shape[1], h, w))
-                frames[k] = img
-            n = det.run_staged(frames)
+            if args.device_jpeg:  # the files go to the device as they are (PoseDetector.run_staged_jpegs)
+                n, route = det.run_staged_jpegs([os.path.join(args.images, images[i][4]) for i in chunk], size=(h, w))
+                for r in route:
+                    routes[r] += 1
+            else:
+                frames = np.empty((len(chunk), h, w, 3), np.uint8)
+                for k, i in enumerate(chunk):
+                    img = read_bgr(os.path.join(args.images, images[i][4]))
+                    if img.shape != (h, w, 3):
+                        raise ValueError("%s is %d x %d, the annotations say %d x %d" % (images[i][4], img.shape[0], img.shape[1], h, w))
+                    frames[k] = img
+                n = det.run_staged(frames)
             recs = K.evaluate_staged(det, 0, n, [K.gt_tables(images[i][3]) for i in chunk])
             fetched = ctx.fetch_results(0, n) if args.results else [None] * n
             for k, i in enumerate(chunk):
@@ -68,6 +75,9 @@ def run_detector(images, args):
                 if args.results:
                     poses, scores, _ = fetched[k]
                     entries[i] = K.results_json(images[i][0], poses, scores)
+    if args.device_jpeg:
+        print("device-jpeg: %d frames decoded on the device, %d by Pillow on the host" % (routes["device"], routes["host"]),
+              file=sys.stderr)
     return records, [e for per_image in entries if per_image for e in per_image]
 
 
@@ -79,6 +89,8 @@ def main(argv=None):
     ap.add_argument("--random-weights", action="store_true", help="seeded random weights: a plumbing run")
     ap.add_argument("--precise", action="store_true", help="multi-scale inference (detect_precise)")
     ap.add_argument("--batch", type=int, default=16, help="frames per staged step")
+    ap.add_argument("--device-jpeg", action="store_true", help="decode baseline JPEG frames on the device, straight into "
+                    "the staged set (PoseDetector.run_staged_jpegs); other files still go through Pillow")
     ap.add_argument("--limit", type=int, default=None, help="only the first K images")
     ap.add_argument("--gpu", type=int, default=0, help="HIP device")
     ap.add_argument("--results", help="write the COCO results JSON of the run here")
@@ -90,8 +102,8 @@ def main(argv=None):
         ap.error("--limit must not be negative")
     args.gpu = max(args.gpu, 0)
     if args.results_in:
-        if args.weights or args.random_weights or args.results:
-            ap.error("--results-in runs no detector: no --weights, --random-weights or --results")
+        if args.weights or args.random_weights or args.results or args.device_jpeg:
+            ap.error("--results-in runs no detector: no --weights, --random-weights, --results or --device-jpeg")
     else:
         if not args.images:
             ap.error("--images is needed to run the detector")

@@ -181,6 +181,44 @@ class PoseDetector(object):
             self._ctx.run_staged()
         return len(frames)
 
+    def run_staged_jpegs(self, items, size=None):
+        """``run_staged`` on JPEG files (``items``: bytes or paths, all of one size) without decoding
+        them on the host: the files the device path takes (baseline, grey or YCbCr 4:4:4 / 4:2:2 /
+        4:2:0; jpeg.py) are entropy-decoded by host threads and finished by kernels straight into the
+        staged set (op_jpeg_stage); every other file is decoded with Pillow, as ``draw.read_bgr``
+        does, and staged as pixels.  ``size``: the (h, w) every frame must have (ValueError otherwise).
+        -> (n, the per-frame route: 'device' or 'host')."""
+        from . import jpeg as _jpeg
+        datas = [_jpeg.file_bytes(i) for i in items]
+        if not datas:
+            raise ValueError("run_staged_jpegs: no frames")
+        bgr, sizes = [None] * len(datas), []
+        for k, d in enumerate(datas):
+            info = _lib.jpeg_probe(d)
+            if info.status != _jpeg.OK:  # outside the subset: Pillow's route from the start
+                bgr[k] = _jpeg.read_bgr_bytes(d)
+                sizes.append(bgr[k].shape[:2])
+            else:
+                sizes.append((info.h, info.w))
+        h, w = size if size is not None else sizes[0]
+        for k, s in enumerate(sizes):
+            if tuple(s) != (h, w):
+                raise ValueError("run_staged_jpegs: frame %d is %d x %d, not %d x %d" % (k, s[0], s[1], h, w))
+        status = self._ctx.stage_jpegs(datas, h, w, bgr)
+        if status.any():  # found out in the scan (corrupt data, a block out of range): Pillow, and stage again
+            for k in np.nonzero(status)[0]:
+                bgr[k] = _jpeg.read_bgr_bytes(datas[k])
+                if bgr[k].shape != (h, w, 3):
+                    raise ValueError("run_staged_jpegs: frame %d is %d x %d, not %d x %d" % ((k,) + bgr[k].shape[:2] + (h, w)))
+            status = self._ctx.stage_jpegs(datas, h, w, bgr)
+            if status.any():
+                raise RuntimeError("run_staged_jpegs: op_jpeg_stage turned down frames given as pixels")
+        if self.precise:
+            self._ctx.run_staged_precise()
+        else:
+            self._ctx.run_staged()
+        return len(datas), ["device" if b is None else "host" for b in bgr]
+
     # ---- crops for the face / hand detectors (restating pose_detector.py:266-425; host-side, used
     # by demo.py).  The arithmetic follows the reference operation for operation (the crop SHA-256
     # fixtures in tests/golden/cpm/ pin it); the structure is this module's own. ----

@@ -882,6 +882,67 @@ int op_keypoint_match_staged(op_ctx* ctx, int32_t first, int32_t n, const int32_
  * op_keypoint_match_staged that completed on `device`; OP_ERR_STATE before the first. */
 int op_keypoint_last_ms(int32_t device, double* ms);
 
+/* ---- baseline JPEG frames decoded on the device (jpeg.py's decode_np is the statement) ----
+ * The subset: SOF0, 8-bit samples, Huffman coding, one interleaved scan, 8-bit quantisation tables,
+ * one component (grey -> B = G = R) or three taken as YCbCr with the luma sampled 1x1, 2x1 or 2x2 and
+ * both chroma components 1x1; restart intervals and custom Huffman tables are decoded, APPn and COM
+ * segments skipped.  The host parses and entropy-decodes (a pool of threads, a frame at a time per
+ * thread); dequantisation, the inverse DCT (libjpeg's jidctint), chroma upsampling (libjpeg's fancy
+ * filters) and YCbCr -> BGR run in two kernels over the whole batch, bit for bit what libjpeg-turbo
+ * (JDCT_ISLOW) writes.  A frame outside the subset is not decoded and not guessed at: it gets a
+ * status, fails no call, and the other frames decode as if it were absent. */
+#define OP_JPEG_OK 0
+#define OP_JPEG_UNSUPPORTED 1 /* well formed, outside the subset (progressive, arithmetic, 12-bit, 4 components,
+                                 an Adobe segment, other sampling factors, 16-bit tables, several scans) */
+#define OP_JPEG_CORRUPT 2     /* truncated data, an undefined Huffman code, a run past coefficient 63, a bad or
+                                 missing marker, a missing table, a wrong restart sequence */
+#define OP_JPEG_SIZE 3        /* op_jpeg_stage: the frame is not the h x w asked for */
+#define OP_JPEG_RANGE 4       /* a block with sum |coef q| > 32768: the 32-bit inverse DCT is not provably exact */
+typedef struct op_jpeg_info {
+  int32_t status;       /* OP_JPEG_*; everything below is 0 unless OP_JPEG_OK */
+  int32_t h, w, components;
+  int32_t hs, vs;       /* the luma's sampling factors (chroma is 1 x 1) */
+  int32_t blocks_w[3], blocks_h[3]; /* each component's padded block grid */
+  int64_t n_blocks;     /* their sum: 64 int16 coefficients each */
+} op_jpeg_info;
+/* Host only: the header parse (through the SOS header) of one file.  The status lies in out->status;
+ * the return value is OP_ERR_INVALID for a null pointer or negative bytes. */
+int op_jpeg_probe(const uint8_t* data, int64_t bytes, op_jpeg_info* out);
+/* Host only: the entropy decode of one file, what jpeg.py's coefficients_np states.  coef (coef_cap
+ * int16; 64 n_blocks are needed, else OP_ERR_INVALID): the quantised coefficients in natural order,
+ * component after component, each component's blocks in raster order over its padded grid; qt
+ * (3 x 64): each component's quantisation table in natural order; *status: OP_JPEG_*. */
+int op_jpeg_coefficients(const uint8_t* data, int64_t bytes, int16_t* coef, int64_t coef_cap, uint16_t* qt,
+                         int32_t* status);
+/* Host only: the predicate behind OP_JPEG_RANGE for one block of 64 coefficients and its table (both
+ * in natural order): *in_range = sum |coef[k] q[k]| <= 32768. */
+int op_jpeg_block_in_range(const int16_t* coef, const uint16_t* q, int32_t* in_range);
+/* Decodes n files (any mix of sizes and samplings) on `device` in one call: out[f] = h w 3 bytes of
+ * BGR pixels (host pointer, sizes from op_jpeg_probe), status[f] = OP_JPEG_*; a frame whose status is
+ * not OP_JPEG_OK leaves out[f] untouched (and may pass a null out[f]).  Arguments are validated
+ * before any device call (OP_ERR_INVALID, the message names the field): n outside 0 .. 65535, null
+ * arrays, a null file, negative bytes, a null image of a decodable frame, more than 2^25 coefficient
+ * blocks.  n == 0, or no decodable frame: OP_OK, no device call (and nothing for op_jpeg_last_ms).
+ * OP_ERR_CAPACITY when the host runs out of memory for the batch's tables (also op_jpeg_stage). */
+int op_jpeg_decode(int32_t device, int32_t n, const uint8_t* const* data, const int64_t* bytes, uint8_t* const* out,
+                   int32_t* status);
+/* op_stage_frames with files instead of pixels: frame f of the staged set comes from bgr[f] (h x w x 3
+ * u8, contiguous) when bgr and bgr[f] are non-null, else from the file data[f]; the kernels write
+ * into the staged set in place, no decoded pixel exists on the host.  A file that is not h x w gets
+ * OP_JPEG_SIZE; the slot of every frame whose status is not OP_JPEG_OK is zero-filled (the caller
+ * decodes those by other means and stages once more with their bgr entries set).  The coefficients
+ * go up from a page-locked buffer of the context in one asynchronous copy on its stream.  Returns
+ * once the frames are staged.  h, w in 8 .. 16384, n in 1 .. 65535. */
+int op_jpeg_stage(op_ctx* ctx, int32_t n, const uint8_t* const* data, const int64_t* bytes, const uint8_t* const* bgr,
+                  int32_t h, int32_t w, int32_t* status);
+/* Threads of the entropy-decode pool: 1 .. 64, or 0 for the default, min(16, the host's hardware
+ * threads); anything else is OP_ERR_INVALID.  A call uses min(decodable frames, threads) of them. */
+int op_jpeg_set_threads(int32_t threads);
+/* ms[0] = the host's entropy-decode wall time, ms[1] = the device time (stream events: uploads and
+ * kernels) of the last op_jpeg_decode or op_jpeg_stage that completed on `device`; OP_ERR_STATE
+ * before the first. */
+int op_jpeg_last_ms(int32_t device, double* ms);
+
 #ifdef __cplusplus
 }
 #endif
