@@ -49,6 +49,8 @@ EXPORTED = (
     "op_keypoint_match", "op_keypoint_match_staged", "op_keypoint_last_ms",
     "op_jpeg_probe", "op_jpeg_coefficients", "op_jpeg_block_in_range", "op_jpeg_decode", "op_jpeg_stage",
     "op_jpeg_set_threads", "op_jpeg_last_ms",
+    "op_haar_create", "op_haar_destroy", "op_haar_detect", "op_haar_candidates", "op_haar_detect_staged",
+    "op_haar_probe", "op_haar_last_ms",
 )
 ARCH = {"facenet": 1, "handnet": 2}
 CPM_PROBE_HI = 256  # OP_CPM_PROBE_HI
@@ -99,6 +101,15 @@ class OpJpegInfo(ctypes.Structure):
                 ("hs", ctypes.c_int32), ("vs", ctypes.c_int32), ("blocks_w", ctypes.c_int32 * 3),
                 ("blocks_h", ctypes.c_int32 * 3), ("n_blocks", ctypes.c_int64)]
 
+
+class OpHaarParams(ctypes.Structure):
+    """op_haar_params (include/openpose_hip.h): detectMultiScale's arguments."""
+    _fields_ = [("scale_factor", ctypes.c_double), ("min_neighbors", ctypes.c_int32), ("min_w", ctypes.c_int32),
+                ("min_h", ctypes.c_int32), ("has_max", ctypes.c_int32), ("max_w", ctypes.c_int32),
+                ("max_h", ctypes.c_int32), ("max_candidates", ctypes.c_int32)]
+
+
+HAAR_MAX_SCALES, HAAR_TIMES = 64, ("total", "grey", "pyramid", "integrals", "cascade")
 
 _lib = None
 
@@ -233,6 +244,13 @@ def lib():
         "op_jpeg_stage": ([P, I32, P, P, P, I32, I32, P], ctypes.c_int),
         "op_jpeg_set_threads": ([I32], ctypes.c_int),
         "op_jpeg_last_ms": ([I32, P], ctypes.c_int),
+        "op_haar_create": ([I32, I32, I32, I32, P, P, I32, P, P, P, P, P, P], ctypes.c_int),
+        "op_haar_destroy": ([P], ctypes.c_int),
+        "op_haar_detect": ([P, I32, P, P, P, P, P, I32, P, P, P, P], ctypes.c_int),
+        "op_haar_candidates": ([P, I32, P, P, P, P, P, I32, P, P, P], ctypes.c_int),
+        "op_haar_detect_staged": ([P, P, I32, I32, P, I32, P, P, P, P], ctypes.c_int),
+        "op_haar_probe": ([P, P, I32, I32, I64, I32, P, P, P, P, P, P, P, P, P], ctypes.c_int),
+        "op_haar_last_ms": ([I32, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -896,6 +914,135 @@ def jpeg_last_ms(device=0):
     ms = (ctypes.c_double * 2)()
     check(lib().op_jpeg_last_ms(int(device), ms), "op_jpeg_last_ms")
     return ms[0], ms[1]
+
+
+def haar_params(scale_factor=1.2, min_neighbors=3, min_size=(1, 1), max_size=None, max_candidates=0):
+    """-> OpHaarParams; sizes are (w, h) as in cv2."""
+    p = OpHaarParams()
+    p.scale_factor, p.min_neighbors = float(scale_factor), int(min_neighbors)
+    p.min_w, p.min_h = int(min_size[0]), int(min_size[1])
+    p.has_max = 0 if max_size is None else 1
+    p.max_w, p.max_h = (0, 0) if max_size is None else (int(max_size[0]), int(max_size[1]))
+    p.max_candidates = int(max_candidates)
+    return p
+
+
+class HaarHandle(object):
+    """An op_haar: a cascade (haar.load_cascade's dict) uploaded to ``device``."""
+
+    def __init__(self, cascade, device=0):
+        self.h = ctypes.c_void_p()
+        self.device = int(device)
+        kinds = dict(stage_first=np.int32, rects=np.int32, win=np.int32)
+        c = {k: np.ascontiguousarray(v, kinds.get(k, np.float32)) for k, v in cascade.items()}  # alive through the call
+        self.win = (int(c["win"][0]), int(c["win"][1]))
+        self.n_stages = len(c["stage_thr"])
+        check(lib().op_haar_create(self.device, self.win[0], self.win[1], self.n_stages, ptr(c["stage_first"]),
+                                   ptr(c["stage_thr"]), len(c["thr"]), ptr(c["rects"]), ptr(c["weights"]), ptr(c["thr"]),
+                                   ptr(c["left"]), ptr(c["right"]), ctypes.byref(self.h)), "op_haar_create")
+
+    def close(self):
+        if self.h:
+            lib().op_haar_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _frames(frames):
+        """-> (arrays kept alive, bgr void*[], hw int32, row_stride int64, channels int32)"""
+        keep = []
+        for f in frames:
+            f = np.asarray(f)
+            if f.dtype != np.uint8 or f.ndim not in (2, 3) or (f.ndim == 3 and f.shape[2] != 3):
+                raise ValueError("a frame is (h, w) or (h, w, 3) uint8, not %s %s" % (f.dtype, f.shape))
+            if f.strides[1:] != ((3, 1) if f.ndim == 3 else (1,)) or f.strides[0] < f.shape[1] * (3 if f.ndim == 3 else 1):
+                f = np.ascontiguousarray(f)
+            keep.append(f)
+        n = len(keep)
+        bgr = (ctypes.c_void_p * max(n, 1))(*[f.ctypes.data for f in keep])
+        hw = np.array([[f.shape[0], f.shape[1]] for f in keep], np.int32).reshape(-1, 2)
+        stride = np.array([f.strides[0] for f in keep], np.int64)
+        channels = np.array([3 if f.ndim == 3 else 1 for f in keep], np.int32)
+        return keep, bgr, hw, stride, channels
+
+    def detect(self, frames, scale_factor=1.2, min_neighbors=3, min_size=(1, 1), max_size=None, max_candidates=0, cap=64):
+        """op_haar_detect -> (rects (n, cap, 4), neighbours (n, cap), count (n,), status (n,)) int32: frame f
+        has count[f] rectangles when status[f] is OP_OK; OP_ERR_CAPACITY: count[f] is what it needs."""
+        keep, bgr, hw, stride, channels = self._frames(frames)
+        n = len(keep)
+        prm = haar_params(scale_factor, min_neighbors, min_size, max_size, max_candidates)
+        rects, neigh = np.zeros((n, cap, 4), np.int32), np.zeros((n, cap), np.int32)
+        count, status = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        check(lib().op_haar_detect(self.h, n, bgr, ptr(hw), ptr(stride), ptr(channels), ctypes.byref(prm), int(cap),
+                                   ptr(rects), ptr(neigh), ptr(count), ptr(status)), "op_haar_detect")
+        return rects, neigh, count, status
+
+    def candidates(self, frames, scale_factor=1.2, min_size=(1, 1), max_size=None, max_candidates=0, cap=4096):
+        """op_haar_candidates -> (rects (n, cap, 4), count (n,), status (n,))."""
+        keep, bgr, hw, stride, channels = self._frames(frames)
+        n = len(keep)
+        prm = haar_params(scale_factor, 0, min_size, max_size, max_candidates)
+        rects = np.zeros((n, cap, 4), np.int32)
+        count, status = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        check(lib().op_haar_candidates(self.h, n, bgr, ptr(hw), ptr(stride), ptr(channels), ctypes.byref(prm), int(cap),
+                                       ptr(rects), ptr(count), ptr(status)), "op_haar_candidates")
+        return rects, count, status
+
+    def detect_staged(self, ctx, first, n, scale_factor=1.2, min_neighbors=3, min_size=(1, 1), max_size=None,
+                      max_candidates=0, cap=64):
+        """op_haar_detect_staged on frames [first, first + n) of ``ctx`` (a Context): as ``detect``."""
+        prm = haar_params(scale_factor, min_neighbors, min_size, max_size, max_candidates)
+        m = max(int(n), 0)
+        rects, neigh = np.zeros((m, cap, 4), np.int32), np.zeros((m, cap), np.int32)
+        count, status = np.zeros(m, np.int32), np.zeros(m, np.int32)
+        check(lib().op_haar_detect_staged(self.h, ctx.h, int(first), int(n), ctypes.byref(prm), int(cap), ptr(rects),
+                                          ptr(neigh), ptr(count), ptr(status)), "op_haar_detect_staged")
+        return rects, neigh, count, status
+
+    def probe(self, frame, scale_factor=1.2, min_size=(1, 1), max_size=None):
+        """op_haar_probe -> [dict(scale, pixels, sum, sqsum, map)] per layer, what haar.result_map_np and
+        haar.pyramid_np state."""
+        keep, bgr, hw, stride, channels = self._frames([frame])
+        prm = haar_params(scale_factor, 0, min_size, max_size, 0)
+        nl = ctypes.c_int32(0)
+        lhw, lsc = np.zeros((HAAR_MAX_SCALES, 2), np.int32), np.zeros(HAAR_MAX_SCALES, np.float32)
+
+        def call(pix, s, q, m, cap):
+            check(lib().op_haar_probe(self.h, bgr[0], int(hw[0, 0]), int(hw[0, 1]), int(stride[0]), int(channels[0]),
+                                      ctypes.byref(prm), ctypes.byref(nl), ptr(lhw), ptr(lsc), ptr(pix), ptr(s), ptr(q),
+                                      ptr(m), ptr(cap)), "op_haar_probe")
+        call(None, None, None, None, None)
+        shapes = []
+        for i in range(nl.value):
+            lh, lw = int(lhw[i, 0]), int(lhw[i, 1])
+            step = 1 if float(lsc[i]) >= 2.0 else 2
+            shapes.append((lh, lw, len(range(0, lh - self.win[1], step)), len(range(0, lw - self.win[0], step))))
+        cap = np.array([sum(a * b for a, b, _, _ in shapes), sum((a + 1) * (b + 1) for a, b, _, _ in shapes),
+                        sum(c * d for _, _, c, d in shapes)], np.int64)
+        pix, s, q = np.zeros(max(cap[0], 1), np.uint8), np.zeros(max(cap[1], 1), np.int32), np.zeros(max(cap[1], 1), np.uint32)
+        m = np.full(max(cap[2], 1), -128, np.int8)
+        if nl.value:
+            call(pix, s, q, m, cap)
+        out, a, b, c = [], 0, 0, 0
+        for i, (lh, lw, gy, gx) in enumerate(shapes):
+            out.append(dict(scale=lsc[i], pixels=pix[a:a + lh * lw].reshape(lh, lw),
+                            sum=s[b:b + (lh + 1) * (lw + 1)].reshape(lh + 1, lw + 1),
+                            sqsum=q[b:b + (lh + 1) * (lw + 1)].reshape(lh + 1, lw + 1), map=m[c:c + gy * gx].reshape(gy, gx)))
+            a, b, c = a + lh * lw, b + (lh + 1) * (lw + 1), c + gy * gx
+        return out
+
+
+def haar_last_ms(device=0):
+    """Device times (ms, stream events) of the last Haar call that completed on ``device``: a dict
+    with the keys of HAAR_TIMES (the whole call, then its grey, pyramid, integral and cascade launches)."""
+    ms = (ctypes.c_double * len(HAAR_TIMES))()
+    check(lib().op_haar_last_ms(int(device), ms), "op_haar_last_ms")
+    return dict(zip(HAAR_TIMES, ms))
 
 
 def body_rois(poses, device=0):

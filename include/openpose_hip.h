@@ -943,6 +943,70 @@ int op_jpeg_set_threads(int32_t threads);
  * before the first. */
 int op_jpeg_last_ms(int32_t device, double* ms);
 
+/* ---- faces from a Haar cascade: cv2's detectMultiScale for new-format stump cascades (haar.py states
+ * it in NumPy -- scales, grey, the integer bilinear pyramid, integrals, setWindow, the stages, the
+ * visiting order with OpenCV's skip after a stage-0 failure, groupRectangles -- and the device equals
+ * that statement bit for bit; parity with an OpenCV build is not pinned).  Per call: grey, one pyramid
+ * launch for every layer of every frame, integrals (row scans, column scans), the cascade (stage 0
+ * densely, the skip rule per row, the later stages over compacted survivor lists), and the candidates
+ * come back as sorted keys; grouping runs on the host.  A batch is worked through in chunks bounded by
+ * a byte budget for the pyramids. */
+typedef struct op_haar op_haar;
+typedef struct op_haar_params {
+  double scale_factor;    /* finite, >= 1.01 */
+  int32_t min_neighbors;  /* <= 0: the candidates ungrouped */
+  int32_t min_w, min_h;   /* >= 1 */
+  int32_t has_max;        /* 0: the frame's own size bounds the window */
+  int32_t max_w, max_h;   /* >= 1 when has_max */
+  int32_t max_candidates; /* per frame on the device; 0: 4096; at most 1048576 */
+} op_haar_params;
+#define OP_HAAR_MAX_SCALES 64
+#define OP_HAAR_TIMES 5 /* op_haar_last_ms: total, grey, pyramid, integrals, cascade */
+/* Uploads a cascade to `device`: a win_w x win_h window (3 .. 64 each), n_stages stages, stage s holding
+ * stumps stage_first[s] .. stage_first[s + 1] - 1 (stage_first[0] = 0, ascending, n_stumps at the end)
+ * and failing below stage_thr[s]; stump j: rects[j][3][4] as x, y, w, h inside the window, weights[j][3]
+ * (a zero third weight: two rects), value < thr[j] ? left[j] : right[j].  OP_ERR_INVALID names the
+ * field. */
+int op_haar_create(int32_t device, int32_t win_w, int32_t win_h, int32_t n_stages, const int32_t* stage_first,
+                   const float* stage_thr, int32_t n_stumps, const int32_t* rects, const float* weights,
+                   const float* thr, const float* left, const float* right, op_haar** out);
+int op_haar_destroy(op_haar* h);
+/* n_frames host images of any mix of sizes: frame f is hw[2f] x hw[2f + 1] pixels of channels[f] (3: BGR,
+ * 1: grey) bytes at bgr[f], row_stride[f] bytes per row.  rects [n_frames][cap][4] (x, y, w, h),
+ * neighbours [n_frames][cap], count [n_frames], status [n_frames]: a frame with more candidates than
+ * params->max_candidates, or more rectangles than cap, gets OP_ERR_CAPACITY and in count what it needs
+ * (the candidates in the first case), the other frames are unaffected and the call returns OP_OK.
+ * Validated before any device call (OP_ERR_INVALID, the message names the field): null pointers, a
+ * scale_factor that is not finite or < 1.01, min / max sizes that are not positive, sides outside
+ * 1 .. 16384, a row_stride below w channels, channels other than 1 and 3, more than 64 scales.  A frame
+ * smaller than the window or exactly its size has no rectangle; n_frames == 0 is OP_OK. */
+int op_haar_detect(const op_haar* h, int32_t n_frames, const uint8_t* const* bgr, const int32_t* hw,
+                   const int64_t* row_stride, const int32_t* channels, const op_haar_params* params, int32_t cap,
+                   int32_t* rects, int32_t* neighbours, int32_t* count, int32_t* status);
+/* The same, ungrouped: the windows that pass every stage in (layer, y, x) order (neighbours is not
+ * taken; min_neighbors is not read). */
+int op_haar_candidates(const op_haar* h, int32_t n_frames, const uint8_t* const* bgr, const int32_t* hw,
+                       const int64_t* row_stride, const int32_t* channels, const op_haar_params* params, int32_t cap,
+                       int32_t* rects, int32_t* count, int32_t* status);
+/* op_haar_detect on frames [first, first + n) of ctx's staged set, read in place on the context's
+ * stream after its queued work: only tables are uploaded, only candidate keys come back.  The cascade
+ * must live on the context's device. */
+int op_haar_detect_staged(const op_haar* h, op_ctx* ctx, int32_t first, int32_t n, const op_haar_params* params,
+                          int32_t cap, int32_t* rects, int32_t* neighbours, int32_t* count, int32_t* status);
+/* One frame, every launch's output.  With pixels == NULL only the plan is returned (no device call):
+ * *n_layers, layer_hw [64][2] (h, w), layer_scale [64].  Otherwise also, layer after layer: pixels
+ * (h w bytes each), sum and sqsum ((h + 1) (w + 1) each) and the int8 result map over the step grid
+ * (haar.result_map_np: n_stages passed, k failed stage k, -1 invalid, -2 skipped); cap[3] = the
+ * elements pixels, sum / sqsum and map can hold (OP_ERR_CAPACITY when too few). */
+int op_haar_probe(const op_haar* h, const uint8_t* bgr, int32_t fh, int32_t fw, int64_t row_stride, int32_t channels,
+                  const op_haar_params* params, int32_t* n_layers, int32_t* layer_hw, float* layer_scale,
+                  uint8_t* pixels, int32_t* sum, uint32_t* sqsum, int8_t* map, const int64_t* cap);
+/* ms[OP_HAAR_TIMES] (stream events) of the last op_haar_detect, op_haar_candidates,
+ * op_haar_detect_staged or op_haar_probe that completed on `device`: the whole call (uploads, kernels,
+ * downloads), then the grey, pyramid, integral and cascade launches summed over its chunks;
+ * OP_ERR_STATE before the first. */
+int op_haar_last_ms(int32_t device, double* ms);
+
 #ifdef __cplusplus
 }
 #endif
