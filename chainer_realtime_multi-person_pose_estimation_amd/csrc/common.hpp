@@ -357,6 +357,10 @@ struct PostBuffers {
 constexpr int kGaussTable = 128;  // doubles in PostBuffers::gauss_w
 constexpr int kGaussGpuOff = 64;  // the GPU-branch taps' offset in it
 constexpr int kMaxGaussR = 16;    // largest radius of the tiled peak kernel (postproc.hip kMaxR)
+// after the GPU-branch taps (at most 2 kMaxGaussR + 1): max(1, their 2-D sum), the factor of the tile
+// early-out in that mode (host_pack.hpp gpu_branch_gain, postproc.hip may_reach_gpu)
+constexpr int kGaussGpuGain = kGaussGpuOff + 2 * kMaxGaussR + 1;
+static_assert(kGaussGpuGain < kGaussTable, "the gain's slot lies inside the table");
 
 struct PostShape {
   int32_t n;             // frames

@@ -88,4 +88,14 @@ inline int gpu_branch_taps(double sigma, int ksize, std::vector<double>& w) {
   return r;
 }
 
+// max(1, S^2) for the sum S of the 1-D factor above: S^2 is the sum of the ksize x ksize kernel.  Not
+// normalised, it is below 1 where the truncation cuts a tail off (0.99876 at sigma 2.5, ksize 17) but
+// ABOVE 1 for sigma <~ 0.7, where the samples of the density overshoot its integral (1.02897 at sigma
+// 0.5, ksize 5): a filtered value can then exceed every source value by that factor.
+inline double gpu_branch_gain(const std::vector<double>& w) {
+  double s = 0.0;
+  for (double v : w) s += v;
+  return s * s > 1.0 ? s * s : 1.0;
+}
+
 }  // namespace op

@@ -7,11 +7,12 @@
 
 #include "common.hpp"
 #include "ctx.hpp"
+#include "host_pack.hpp"
 
 namespace op {
 
 // The device Gaussian table (PostBuffers::gauss_w): the CPU-branch taps (scipy's normalised 2r + 1)
-// at 0, the GPU-branch 1-D factor (op_set_peak_mode) at kGaussGpuOff
+// at 0, the GPU-branch 1-D factor (op_set_peak_mode) at kGaussGpuOff, its early-out factor at kGaussGpuGain
 std::vector<double> gauss_table(const op_ctx* c) {
   // (a sigma whose radius passes kMaxR -- 2r + 1 > 33 taps -- is refused by check_shape before any
   // launch; its table is cut at the region's end rather than written past it)
@@ -20,6 +21,7 @@ std::vector<double> gauss_table(const op_ctx* c) {
   const size_t ng = std::min<size_t>(c->gpu_taps.size(), op::kGaussTable - op::kGaussGpuOff);
   std::copy(c->gauss_host.begin(), c->gauss_host.begin() + nc, t.begin());
   std::copy(c->gpu_taps.begin(), c->gpu_taps.begin() + ng, t.begin() + op::kGaussGpuOff);
+  if (ng) t[op::kGaussGpuGain] = op::gpu_branch_gain(c->gpu_taps);
   return t;
 }
 

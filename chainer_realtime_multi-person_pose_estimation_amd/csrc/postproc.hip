@@ -873,8 +873,21 @@ struct HeatFull {  // already-upsampled planes: frame f, joint j at p + f*fs + j
 // values (bilinear f32 weights >= 0 summing to 1 within 4 ulp, normalised non-negative Gaussian taps
 // in f64, two f32 roundings), so it is <= M + |M| * 1e-6 for the source maximum M.  A tile whose
 // sources all stay below thresh - |.| * 1e-4 cannot hold a value > thresh, hence no peak.
+// ASSUMES taps that sum to at most 1 and a boundary that repeats source values (reflection): the CPU
+// branch only.
 __device__ __forceinline__ bool may_reach(float v, float thresh) {
   return (double)v + fabs((double)v) * 1e-4 >= (double)thresh;
+}
+
+// The same for the GPU branch (G), where neither assumption holds.  Its taps are the reference's
+// unnormalised kernel, whose sum S^2 passes 1 for sigma <~ 0.7 (host_pack.hpp gpu_branch_gain), and
+// its zero padding mixes 0 into the values next to the map border.  A filtered value is a
+// non-negative combination, of total weight <= S^2, of upsampled values <= M and of zeros: at most
+// max(M, 0) * gain with gain = max(1, S^2), read from the tap table.  (A threshold <= 0 keeps every
+// tile: the padding's 0 already reaches it.)
+__device__ __forceinline__ bool may_reach_gpu(float v, float thresh, double gain) {
+  const double u = v > 0.0f ? (double)v * gain : 0.0;
+  return u + u * 1e-4 >= (double)thresh;
 }
 
 // R > 0: radius fixed at compile time (register-blocked passes, NV outputs per thread); R == 0: any
@@ -967,15 +980,21 @@ __global__ __launch_bounds__(kFN) void heat_fused(Src src, int mh, int mw, const
     const int c = src.src.heat_off + j;
     float* win = tmp;
     bool live = !staged;
+    [[maybe_unused]] double gain = 1.0;
+    if constexpr (G) gain = w[kGaussGpuGain - kGaussGpuOff];  // w: the GPU-branch taps at kGaussGpuOff
     if (staged)
       for (int i = threadIdx.x; i < nwy * nwx; i += kFN) {
         const int a = i / nwx;
         const float v = m.at(c, wy + a, wx + (i - a * nwx));
         win[i] = v;
-        live |= may_reach(v, thresh);
+        if constexpr (G)
+          live |= may_reach_gpu(v, thresh, gain);
+        else
+          live |= may_reach(v, thresh);
       }
     // No low-res value of the window can lift the upsampled + smoothed tile above the peak
-    // threshold: the tile has no peak, skip the passes (result identical, see may_reach).
+    // threshold: the tile has no peak, skip the passes (result identical, see may_reach and, for
+    // G, may_reach_gpu).
     if (block_none(live, &any_live)) return;
     for (int i = threadIdx.x; i < ur * uc; i += kFN) {
       const int ly = i / uc, lx = i - ly * uc;

@@ -1,15 +1,19 @@
-"""GPU-branch peak semantics (op_set_peak_mode, include/openpose_hip.h) against the oracle's
-restatement of the reference's GPU branch (pose_detector.py:38-44, 111-132; oracle/postproc.py
-compute_peaks_gpu_branch).
+"""GPU-branch peak semantics (op_set_peak_mode, include/openpose_hip.h) against the reference's GPU
+branch (pose_detector.py:38-44, 111-132): against fixtures its own code made under a NumPy-backed
+``xp`` with the convolution stood in by the exact sum (tests/golden/gpu_branch/,
+make_golden_gpu_branch.py; gpu_branch_cases.py lists the (sigma, ksize) sets and cases), and against
+the oracle's restatement (oracle/postproc.py compute_peaks_gpu_branch), which
+test_gpu_branch_golden.py holds to the same fixtures bit for bit.
 
-Parity unpinned against the reference itself (its GPU branch needs CUDA + cuDNN, so no fixture of
-it exists).  The device filter is separable f64 with one f32 rounding between the passes; the oracle
-is the exact 2-D sum rounded once.  Tolerance: peak sets and poses exact (no peak decision of the
-inputs lies within 5e-7 of a tie relative to the map maximum, asserted below), scores within 1e-6
-relative."""
+The device filter is separable f64 with one f32 rounding between the passes; the reference's stand-in
+and the oracle are the exact 2-D sum rounded once.  Tolerance: peak sets and poses exact (no peak
+decision of the golden inputs lies within 5e-7 of a tie relative to the map maximum, asserted below;
+none of the fixtures' within 5e-6, asserted by their generator; the two forms differ by at most
+9.4e-8, test_gpu_branch_golden.py), scores within 1e-6 relative."""
 import numpy as np
 import pytest
 
+import gpu_branch_cases as GC
 from conftest import golden_cases, load_golden, people_image
 from oracle import postproc as P
 
@@ -26,23 +30,15 @@ def gctx(lib, rand_weights):
     c.close()
 
 
-def _decision_margin(heat_low, orig_h, orig_w):
+def _decision_margin(heat_low, orig_h, orig_w, params=P.PARAMS):
     """Relative room a rounding difference has before one peak decision flips: for a peak, its
     smallest gap to the threshold or a neighbour; for any other pixel, its largest failing gap (all
-    of them must flip to make it a peak).  Neighbours outside the map count as 0."""
+    of them must flip to make it a peak).  Neighbours outside the map count as 0
+    (gpu_branch_cases.decision_margin, on the oracle's filtered maps)."""
     from oracle import cvresize
-    mw, mh = cvresize.compute_optimal_size(orig_h, orig_w, 320)
-    f = P.gpu_branch_filter(P.resize_images(heat_low, mh, mw)[:-1]).astype(np.float64)
-    pad = np.pad(f, ((0, 0), (1, 1), (1, 1)))
-    g = [f - np.float64(np.float32(0.05))]
-    for dy, dx in ((0, 1), (2, 1), (1, 0), (1, 2)):
-        g.append(f - pad[:, dy:dy + f.shape[1], dx:dx + f.shape[2]])
-    g = np.stack(g)
-    peak = (g[0] > 0) & np.all(g[1:] >= 0, axis=0)
-    m_peak = np.where(peak, np.abs(g).min(axis=0), np.inf)
-    fail = np.where(np.concatenate([(g[0] <= 0)[None], g[1:] < 0]), np.abs(g), 0.0)
-    m_non = np.where(~peak, fail.max(axis=0), np.inf)
-    return min(float(m_peak.min()), float(m_non.min())) / max(float(f.max()), 1e-30)
+    mw, mh = cvresize.compute_optimal_size(orig_h, orig_w, params["heatmap_size"])
+    return GC.decision_margin(P.gpu_branch_filter(P.resize_images(heat_low, mh, mw)[:-1], params),
+                              params["heatmap_peak_thresh"])
 
 
 @pytest.mark.parametrize("case", golden_cases())
@@ -104,6 +100,142 @@ def test_gpu_branch_staged_batch_equals_single(gctx, graph):
                 assert np.array_equal(p, single[i][0]) and np.array_equal(s, single[i][1])
     finally:
         gctx.use_staged_maps(False)
+
+
+# ---- every kernel size and sigma, against the reference's own GPU branch (tests/golden/gpu_branch/) ----
+def _params(set_name, case):
+    return dict(P.PARAMS, **GC.overrides(set_name, case))
+
+
+def _context_key(set_name, case):
+    prm = _params(set_name, case)
+    return prm["gaussian_sigma"], prm["heatmap_size"]
+
+
+@pytest.fixture(scope="module")
+def sigma_contexts(lib, rand_weights):
+    """get(set, case): the one live Context of the pair's (gaussian_sigma, heatmap_size), switched to
+    the set's ksize (the previous parameters' context is closed)."""
+    live = {}
+
+    def get(set_name, case):
+        key = _context_key(set_name, case)
+        if key not in live:
+            for c in live.values():
+                c.close()
+            live.clear()
+            live[key] = lib.Context(0, lib.params_from_dict(_params(set_name, case)), lib.OpLimits())
+            live[key].set_weights(rand_weights)
+        live[key].set_peak_mode("gpu", GC.SETS[set_name][1])
+        return live[key]
+
+    yield get
+    for c in live.values():
+        c.close()
+
+
+def _check_fixture(d, out):
+    """A (poses, scores, res) result against a fixture of the reference's GPU branch.  The single-scale
+    path returns no peak list: the peaks are held by their count and by the keypoint coordinates of
+    the poses (every peak of `seam` and most of the others' are part of one)."""
+    poses, scores, res = out
+    assert int(d["status"]) == 0
+    assert (res.map_h, res.map_w) == (int(d["map_h"]), int(d["map_w"]))
+    assert res.n_peaks == len(d["all_peaks"])
+    assert res.n_persons == len(d["scores"])
+    assert np.array_equal(poses.reshape(d["poses"].shape), d["poses"])
+    assert np.allclose(scores, d["scores"], rtol=SCORE_RTOL, atol=0)
+
+
+@pytest.mark.parametrize("set_name,case", sorted(GC.pairs(), key=lambda p: _context_key(*p)))
+def test_gpu_branch_postprocess_vs_reference(sigma_contexts, set_name, case):
+    """heat_fused<HeatLow, 0, true> at radius 1, 2, 3, 4 and 16 and <HeatLow, 8, true>: zero padding at
+    the map border (`border`), peaks on both sides of a tile seam (`seam`), and a tile whose sources
+    all lie below the threshold while the kernel, summing to more than 1, lifts one value over it
+    (`subthresh`: the early-out of may_reach)."""
+    ctx = sigma_contexts(set_name, case)
+    paf_low, heat_low, oh, ow = GC.load_inputs(case)
+    _check_fixture(GC.load_fixture(set_name, case), ctx.postprocess(paf_low, heat_low, oh, ow))
+
+
+@pytest.mark.parametrize("set_name", ["s25_k5", "s05_k5"])
+def test_gpu_branch_nine_staged_frames(sigma_contexts, set_name):
+    """Nine staged frames (more than 8: the XCD-major block order; not a multiple of 8: the blocks of
+    the padded grid that leave at f >= n_frames), eager and as a graph replayed twice: each frame
+    equals its single-frame result bit for bit, and the reference's fixture."""
+    cases = ["six_people", "border", "coincident"]
+    ctx = sigma_contexts(set_name, cases[0])
+    inputs = {c: GC.load_inputs(c) for c in cases}
+    assert len({(i[0].shape, i[2], i[3]) for i in inputs.values()}) == 1
+    oh, ow = inputs[cases[0]][2:]
+    order = [cases[i % len(cases)] for i in range(9)]
+    single = {c: ctx.postprocess(*inputs[c]) for c in cases}
+    for c in cases:
+        _check_fixture(GC.load_fixture(set_name, c), single[c])
+    ctx.stage_frames(np.zeros((len(order), oh, ow, 3), np.uint8))
+    ctx.stage_maps(np.stack([np.concatenate(inputs[c][:2]) for c in order]))
+    ctx.use_staged_maps(True)
+    try:
+        for graph in (False, True, True):
+            ctx.run_staged(graph=graph)
+            ctx.synchronize()
+            for i, c in enumerate(order):
+                p, s, r = ctx.fetch_result(i)
+                assert r.n_peaks == single[c][2].n_peaks
+                assert np.array_equal(p, single[c][0]) and np.array_equal(s, single[c][1])
+                _check_fixture(GC.load_fixture(set_name, c), (p, s, r))
+    finally:
+        ctx.use_staged_maps(False)
+
+
+def test_peak_mode_switches_rewrite_the_taps(lib, rand_weights):
+    """gpu/5 -> gpu/17 -> cpu -> gpu/33 -> gpu/3 on one context: every step gives its own fixture (the
+    CPU golden, bit for bit, for the cpu step), so the tap table at kGaussGpuOff is rewritten by each
+    switch, not appended to or left over from a longer kernel."""
+    c = lib.Context(0)
+    try:
+        c.set_weights(rand_weights)
+        args = GC.load_inputs("six_people")
+        for mode, ksize in (("gpu", 5), ("gpu", 17), ("cpu", None), ("gpu", 33), ("gpu", 3)):
+            c.set_peak_mode(mode, ksize)
+            out = c.postprocess(*args)
+            if mode == "gpu":
+                _check_fixture(GC.load_fixture("s25_k%d" % ksize, "six_people"), out)
+            else:
+                d = load_golden("six_people")
+                assert out[2].n_peaks == len(d["all_peaks"])
+                assert np.array_equal(out[0].reshape(d["poses"].shape), d["poses"]) and np.array_equal(out[1], d["scores"])
+    finally:
+        c.close()
+
+
+def test_map_not_above_the_gpu_radius_refused(lib):
+    """heatmap_size 16 -> a 16 x 16 map, not above the GPU branch's radius 16 at ksize 33: refused by
+    check_shape ahead of the first launch (maps no larger than the radius stay unsupported in this
+    mode), and the context stays usable: the same map at ksize 5 against the restatement, and a
+    96 x 96 map through the standalone peaks."""
+    paf_low, heat_low, _, _ = GC.load_inputs("subthresh")
+    heat_low = heat_low * np.float32(4)  # the bump well above the threshold
+    prm = dict(P.PARAMS, heatmap_size=16)
+    c = lib.Context(0, lib.params_from_dict(prm), lib.OpLimits())
+    try:
+        c.set_peak_mode("gpu", 33)
+        with pytest.raises(ValueError, match="outside kernel limits"):
+            c.postprocess(paf_low, heat_low, 96, 96)
+        assert lib.last_error()
+        c.set_peak_mode("gpu", 5)
+        p5 = dict(prm, ksize=5)
+        assert _decision_margin(heat_low, 96, 96, p5) > GC.MARGIN_FLOOR
+        _, _, dbg = P.postprocess(paf_low, heat_low, 96, 96, p5, return_debug=True, branch="gpu")
+        _, _, res = c.postprocess(paf_low, heat_low, 96, 96)
+        assert (res.map_h, res.map_w) == (16, 16) and res.n_peaks == len(dbg["all_peaks"]) == 1
+        c.set_peak_mode("gpu", 33)
+        full = P.resize_images(heat_low, 96, 96)
+        want = P.compute_peaks_from_heatmaps(full, prm)
+        assert len(want) == 1
+        assert np.array_equal(c.compute_peaks(full).reshape(-1, 5), np.asarray(want).reshape(-1, 5))
+    finally:
+        c.close()
 
 
 def _near_ties(heat_low, orig_h, orig_w, eps=1e-6):

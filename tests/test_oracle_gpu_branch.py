@@ -2,12 +2,14 @@
 checked on the CPU: the kernel against its formula, the zero-padded filter against SciPy's
 correlate (mode 'constant'), and the >= NMS against the strict CPU branch on a plateau.
 
-Parity unpinned against the reference itself: its GPU branch needs CUDA + cuDNN (absent here), so no
-fixture of it exists; these checks pin the restatement to the reference's formulas."""
+The restatement is pinned to the reference's own branch (run under a NumPy-backed ``xp``, the
+convolution stood in by the exact sum) by the fixtures of tests/golden/gpu_branch/:
+test_gpu_branch_golden.py; these checks pin it to the reference's formulas."""
 import numpy as np
 import pytest
 from scipy import ndimage
 
+from gpu_branch_cases import separable_like_the_device as _separable_like_the_device
 from oracle import postproc as P
 
 
@@ -55,22 +57,6 @@ def test_peak_rows_order_and_ids():
     assert np.all(np.diff(key) > 0)
     assert np.array_equal(g[:, 4], np.arange(len(g)))
     assert np.all(g[:, 3] > 0.05)
-
-
-def _separable_like_the_device(h, sigma=2.5, ksize=17):
-    """The device's arithmetic for the GPU branch (postproc.hip heat_fused<.., G>): the 1-D factor
-    g(d) = exp(-d^2 / 2 s^2) / sqrt(2 pi s^2) (host_pack.hpp gpu_branch_taps), a vertical then a
-    horizontal pass in f64 over zero-padded f32 maps, rounded to f32 after each pass."""
-    r = ksize // 2
-    d = np.arange(-r, r + 1, dtype=np.float64)
-    g = np.exp(-0.5 * d * d / (sigma * sigma)) / np.sqrt(2.0 * np.pi * sigma * sigma)
-    J, H, W = h.shape
-    p = np.zeros((J, H + 2 * r, W), np.float64)
-    p[:, r:r + H] = h
-    v = sum(g[k] * p[:, k:k + H] for k in range(ksize)).astype(np.float32)
-    q = np.zeros((J, H, W + 2 * r), np.float64)
-    q[:, :, r:r + W] = v
-    return sum(g[k] * q[:, :, k:k + W] for k in range(ksize)).astype(np.float32)
 
 
 def test_device_arithmetic_within_rounding_of_the_restatement():
